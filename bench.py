@@ -9,7 +9,13 @@ Default workload = BASELINE.json configs[1]: REDCLIFF-S w/ state smoothing, D4IC
 windows of 21 steps, labels (N, K, 1)); D4IC itself is not in the image, so the windows
 are synthetic with the same shapes.
 
-    python bench.py [--gpus N --steps K --warmup W] [--mode fit|dp]
+    python bench.py [--gpus N --steps K --warmup W] [--mode fit|dp] [--full] [--dump-outputs DIR]
+
+A plain run does what the headline figure needs and no more: set up, W warm-up steps, the preheat,
+K timed steps, one JSON line.  --full adds every other leg (per-kernel times and rooflines, the
+packed grid search, fits/hour, the reference's grids, the north-star and stress configs, the
+data-parallel leg, the CPU baselines); the options that size or skip those legs act only with it.
+--dump-outputs DIR writes what the timed steps left behind (dump_outputs) as DIR/<name>.npy.
 
 --gpus N > 1 without a torch.distributed launcher: this process starts N ranks itself
 (torch.distributed.run, 127.0.0.1) before touching the GPU and exits with their status.
@@ -351,6 +357,63 @@ def preheat(plan, start, seconds):
         torch.cuda.synchronize()
         n += 20
     return n
+
+
+def fit_state(eng):
+    """The tensors a training step of a single fit updates in place: the packed parameters, the
+    BatchNorm running statistics and batch counter, the workspace (it carries the adjacency
+    supports from one step to the next), both Adam moment pairs."""
+    return ([eng.emb, eng.fac, eng.bn, eng.dgcnn.BN1.num_batches_tracked, eng.ws]
+            + [eng.opt[g][k] for g in ("A", "B") if eng.opt[g] is not None for k in ("m", "v")])
+
+
+def save_fit_state(eng):
+    return ([t.clone() for t in fit_state(eng)],
+            dict((g, eng.opt[g]["t"]) for g in ("A", "B") if eng.opt[g] is not None), eng.supports_fresh)
+
+
+def restore_fit_state(eng, saved):
+    """Put a save_fit_state() back, so that the steps in between (the preheat, whose number depends
+    on the clock) leave no trace: the timed steps then start from the state the W warm-up steps
+    left, the same in every run."""
+    tensors, steps, fresh = saved
+    with torch.no_grad():
+        for t, s in zip(fit_state(eng), tensors):
+            t.copy_(s)
+    for g, t in steps.items():
+        eng.opt[g]["t"] = t
+    eng._sync_steps()
+    if fresh:  # the supports came back with the workspace: no rebuild in the first timed step
+        eng._mark_fresh()
+    else:
+        eng.invalidate()
+
+
+DUMP_BYTES = 64 * 1000 * 1000  # --dump-outputs writes at most this much in all
+
+
+def dump_outputs(path, eng):
+    """What a caller of the timed path holds after its last step, as <path>/<name>.npy (float32; the
+    integer batch counter as float64): every entry of the model's state_dict (parameters and
+    BatchNorm buffers, `<key>.npy`) and the Adam moments of both optimizers
+    (`adam_{A,B}.{exp_avg,exp_avg_sq}.npy`, flat in the engine's packed parameter order).  When all
+    of it exceeds DUMP_BYTES, every array of more than 4096 elements is cut to the same fraction of
+    its (flattened) elements, at sorted indices drawn by RandomState(0): a fixed sample."""
+    torch.cuda.synchronize()
+    arrays = dict((k, v.detach().cpu().numpy()) for k, v in eng.model.state_dict().items())
+    for g in ("A", "B"):
+        if eng.opt[g] is not None:
+            arrays["adam_%s.exp_avg" % g] = eng.opt[g]["m"].detach().cpu().numpy()
+            arrays["adam_%s.exp_avg_sq" % g] = eng.opt[g]["v"].detach().cpu().numpy()
+    arrays = dict((k, a.astype(np.float32 if a.dtype.kind == "f" and a.itemsize <= 4 else np.float64))
+                  for k, a in arrays.items())
+    total = sum(a.nbytes for a in arrays.values())
+    os.makedirs(path, exist_ok=True)
+    for k, a in arrays.items():
+        if total > DUMP_BYTES and a.size > 4096:
+            keep = max(4096, int(a.size * 0.9 * DUMP_BYTES / total))
+            a = a.reshape(-1)[np.sort(np.random.RandomState(0).choice(a.size, keep, replace=False))]
+        np.save(os.path.join(path, k + ".npy"), a)
 
 
 def single_fit(c, args, dev, rank, nbatch=32):
@@ -711,18 +774,23 @@ def mode_fit(args, dev, rank, world, dist, holder):
     B = c["B"]
     eng, plan = single_fit(c, args, dev, rank)
     plan(args.warmup, 0).run()
+    warm = save_fit_state(eng)
     extra = preheat(plan, args.warmup, args.preheat_s)
-    p_timed = plan(args.steps, args.warmup + extra)
+    restore_fit_state(eng, warm)  # the preheat only keeps the device busy: its steps are undone
+    p_timed = plan(args.steps, args.warmup)
     elapsed = timed(p_timed.run, dist, dev)
     value = world * args.steps * B / elapsed
+    if args.dump_outputs and rank == 0:
+        dump_outputs(args.dump_outputs, eng)
 
     out = {"metric": METRIC, "value": round(value, 1), "unit": "windows/s", "n_gpus": world, "steps": args.steps,
            "warmup": args.warmup, "ms_per_step": round(1e3 * elapsed / args.steps, 4), "higher_is_better": True,
-           "scaling": "weak", "vs_baseline": None, "dtype": "f32",
+           "scaling": "weak", "vs_baseline": None, "dtype": "f32", "full": args.full,
            "data": "synthetic (D4IC/sVAR-shaped windows; datasets not in image)",
            "preheat": {"seconds": args.preheat_s, "extra_untimed_steps": extra,
                        "note": "untimed steps after the W warm-up steps until the device has been busy this long "
-                               "(clock ramp after the host-side setup); the timed region is exactly `steps` steps"},
+                               "(clock ramp after the host-side setup), then undone: the timed region is exactly "
+                               "`steps` steps from the state the warm-up steps left"},
            "config": {"workload": c["workload"], "global_batch": B * world, "windows_per_step_per_gpu": B,
                       "parallelism": "replicas%d (one independent fit per GPU, no collective)" % world,
                       "ranks": world, "flops_per_window": flops_per_window(c)["total"]}}
@@ -893,6 +961,8 @@ def mode_dp(args, dev, rank, world, dist, holder=None):
     elapsed, dp = dp_throughput(B, args.steps, args.warmup, dev, dist)
     if rank != 0:
         return None
+    if args.dump_outputs:
+        dump_outputs(args.dump_outputs, dp.eng)  # rank 0's copy (the ranks' models stay identical)
     value = args.steps * B / elapsed
     return {"metric": METRIC, "value": round(value, 1), "unit": "windows/s", "n_gpus": world, "steps": args.steps,
             "warmup": args.warmup, "ms_per_step": round(1e3 * elapsed / args.steps, 4), "higher_is_better": True,
@@ -1014,7 +1084,15 @@ def main():
     # 512 = the most windows one launch takes (Bmax), so one rank can run the same global batch
     ap.add_argument("--dp-leg-batch", type=int, default=512,
                     help="global batch of the data-parallel leg of --mode fit (0: skip)")
+    ap.add_argument("--full", action="store_true",
+                    help="also run every leg beside the headline figure (kernel times and rooflines, packed grid, "
+                         "fits/hour, reference grids, north-star and stress configs, data-parallel leg, CPU baselines)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write what they computed as DIR/<name>.npy (dump_outputs)")
     args = ap.parse_args()
+    if not args.full:  # a plain run: the headline figure only
+        args.no_cpu_baseline = args.no_kernel_times = args.no_north_star = True
+        args.replicas, args.fit_replicas, args.ref_grid_epochs, args.c5_steps, args.dp_leg_batch = 1, 0, 0, 0, 0
 
     if args.gpus > 1 and "WORLD_SIZE" not in os.environ:
         import __graft_entry__
