@@ -34,8 +34,10 @@ extern "C" {
  * 9: redcliff_factor_forward writes finished predictions y_out[r][B][K][p] (callers no longer decode
  *    the kernel-private workspace); redcliff_factor_forward_workspace_floats sizes its workspace;
  *    redcliff_step_predictions reads a step's predictions back the same way; RedcliffAdamHyper.t_offset
- *    (was padding) offsets a replica's Adam step number from the launch's */
-#define REDCLIFF_ABI_VERSION 9
+ *    (was padding) offsets a replica's Adam step number from the launch's
+ * 10: the cEmbedder chain: redcliff_cemb_param_count / _workspace_bytes / _workspace_regions /
+ *    _train_step / _train_steps and RedcliffCEmbArgs (existing entries and layouts unchanged) */
+#define REDCLIFF_ABI_VERSION 10
 
 /* error codes (negative) */
 #define REDCLIFF_EINVAL (-1)  /* bad dimension / pointer                        */
@@ -282,6 +284,53 @@ int redcliff_gc_progress_grouped(int32_t S, int32_t spt, int32_t nE, int32_t G, 
  * One workgroup per row / pair, reductions in a fixed order independent of the launch size. */
 int redcliff_gc_track_stats(int32_t n_l1_rows, int64_t l1_len, const float* est, double* l1_out, int32_t n_samples,
                             int32_t K, int64_t row_len, const float* nolag, double* dots_out, void* stream);
+
+/* ---- cEmbedder chain (models/redcliff_factor_score_embedders.py:183-331) ----------------------
+ * The embedder is K copies of models/cmlp.py:12-35 MLP (Conv1d(p, eh, F) -> ReLU -> Conv1d(eh, 1, 1)),
+ * one per factor score, on the embedder window X[row][Lmax-F : Lmax].
+ *
+ * Packed cEmbedder parameter layout (floats, per replica):
+ *   We0[K][eh][p][F] | be0[K][eh] | We1[K][eh] | be1[K]
+ * (We0[k] is the Conv1d(p, eh, F) weight of network k: columns q = c*F + t, as the factors' W0.)
+ *
+ * Limits: p <= 64, K <= 16, h <= 128, eh <= 128, L <= F <= 64, Bmax <= 512, and the matrix-core
+ * factor chain's LDS tiles at Bmax windows; outside them every entry below fails with
+ * REDCLIFF_ELIMIT (the size queries return 0) and a redcliff_last_error message.  The n / H / M1
+ * fields of RedcliffDims are ignored (pass 1, which keeps the shared workspace small). */
+size_t redcliff_cemb_param_count(const RedcliffDims* d, int32_t eh);
+
+/* Bytes of the second, cEmbedder-private workspace for d->R replicas: hidden activations
+ * ha[K][Bmax][eh], the We1 snapshot, the embedder group norms g[K][p][F] / g0[K][p]
+ * (models/redcliff_factor_score_embedders.py:297-326), the fixed embedder graph E[p][p][Ls] /
+ * E0[p][p] (sum_k g_k g_k^T, ...withStateSmoothing.py:500-519), its per-factor gradient records
+ * dE[K][p][p][Ls] and dL/dw_raw[Bmax][K].  Laid out with the shared workspace's region /
+ * guard-band mechanism (redcliff_debug_guard_bands applies). */
+size_t redcliff_cemb_workspace_bytes(const RedcliffDims* d, int32_t eh);
+/* (start, size) pairs, in floats, of the regions of one replica's slice of that workspace in layout
+ * order: ha w1 g g0 E E0 dE draw; when n_pairs allows, one more pair (slice size, 0).  Returns the
+ * region count (8). */
+int redcliff_cemb_workspace_regions(const RedcliffDims* d, int32_t eh, int64_t* out, int32_t n_pairs);
+
+typedef struct RedcliffCEmbArgs {
+  int32_t eh;            /* cEmbedder hidden width (hidden == [eh])                           */
+  int32_t pad_;
+  void* ws; size_t ws_bytes; /* the cEmbedder workspace (redcliff_cemb_workspace_bytes)        */
+} RedcliffCEmbArgs;
+
+/* One batch_update (...withStateSmoothing.py:734-933) of a model whose factor-score embedder is the
+ * cEmbedder: conditional_factor_fixed_embedder GC (:500-519, :565-580), factor weights applied
+ * after simulation (:326-385), num_sims == 1, the loss of :624-731.  RedcliffStepArgs as in
+ * redcliff_train_step with emb / emb_m / emb_v / emb_stride the packed cEmbedder group; the bn_*
+ * fields are ignored.  Flags and phases as redcliff_train_step (RC_BN_TRAIN is ignored: no
+ * BatchNorm); RC_GRAD_ONLY and RC_REFRESH_SUPPORTS are rejected with REDCLIFF_EINVAL.  With
+ * RC_VALUES and no RC_STEP_* it is the per-batch body of validate_training (:1650-1790).  R >= 1
+ * replicas with strides and the `replicas` list as redcliff_train_step; one stream, no
+ * cross-replica state, every reduction in a fixed order. */
+int redcliff_cemb_train_step(const RedcliffStepArgs* a, const RedcliffCEmbArgs* e, void* stream);
+/* nsteps consecutive batch_updates as redcliff_train_steps: step i uses rows[i] / sizes[i] and
+ * Adam step numbers a->tA + i (a->tB + i) for the stepped groups. */
+int redcliff_cemb_train_steps(const RedcliffStepArgs* a, const RedcliffCEmbArgs* e, int32_t nsteps,
+                              const int64_t* rows, const int32_t* sizes, void* stream);
 
 /* Per-kernel HIP-event timing for benchmarking: redcliff_kernel_timing(1) brackets every
  * kernel launched by redcliff_train_step with events on its stream; redcliff_kernel_times()

@@ -219,12 +219,13 @@ int redcliff_dgcnn_supports(const RedcliffDims* d, const float* emb, int64_t emb
   return rc_launch_supports(*d, emb, emb_stride, (float*)ws, wo.total, rc_emb_off(*d), wo, (hipStream_t)stream);
 }
 
-static int make_ctx(const RedcliffStepArgs* a, StepCtx& c) {
+// cemb: a cEmbedder step (redcliff_cemb_train_step), which has no BatchNorm buffers
+static int make_ctx(const RedcliffStepArgs* a, StepCtx& c, bool cemb = false) {
   int e = check_dims(&a->d);
   if (e) return e;
   const RedcliffDims& d = a->d;
   if (a->B < 1 || a->B > d.Bmax) { rc_set_error("batch %d outside [1, Bmax=%d]", a->B, d.Bmax); return REDCLIFF_EINVAL; }
-  if (!a->X || !a->emb || !a->fac || !a->hyper || !a->ws || !a->bn_rm || !a->bn_rv) {
+  if (!a->X || !a->emb || !a->fac || !a->hyper || !a->ws || (!cemb && (!a->bn_rm || !a->bn_rv))) {
     rc_set_error("null buffer in step arguments");
     return REDCLIFF_EINVAL;
   }
@@ -305,6 +306,7 @@ static int make_ctx(const RedcliffStepArgs* a, StepCtx& c) {
   rc_emb_partial_layout(c, rc_emb_use_gemm(d));
   c.fslots = rc_fac_slots(d);
   rc_ctx_magics(c);
+  c.cE = nullptr; c.cdE = nullptr; c.cwss = 0;
   return 0;
 }
 
@@ -505,6 +507,120 @@ int redcliff_train_steps(const RedcliffStepArgs* a, int32_t nsteps, const int64_
     s.tB = a->tB + ((a->flags & RC_STEP_B) ? i : 0);
     if (a->bn_stats) s.bn_stats = a->bn_stats + (int64_t)i * bn_stats_step;
     const int e = redcliff_train_step(&s, stream);
+    if (e) return e;
+  }
+  return 0;
+}
+
+// ---- cEmbedder chain (rc_cemb.hip) --------------------------------------------------------------
+// The shared dims with the DGCNN-only fields set to 1 (they are ignored), checked against the
+// common limits plus eh and the LDS needs of the matrix-core factor chain at Bmax windows.
+static int cemb_dims(const RedcliffDims* din, int32_t eh, RedcliffDims& d) {
+  if (!din) { rc_set_error("null dims"); return REDCLIFF_EINVAL; }
+  d = *din;
+  d.n = d.H = d.M1 = 1;
+  int e = check_dims(&d);
+  if (e) return e;
+  if (eh < 1) { rc_set_error("invalid cEmbedder hidden width eh=%d", eh); return REDCLIFF_EINVAL; }
+  if (eh > 128 || !rc_fac_mfma_fits(d, true)) {
+    rc_set_error("dims outside cEmbedder kernel limits (p<=64 K<=16 h<=128 eh<=128 L<=F<=64 Bmax<=512, factor-chain LDS at Bmax)");
+    return REDCLIFF_ELIMIT;
+  }
+  return 0;
+}
+
+size_t redcliff_cemb_param_count(const RedcliffDims* d, int32_t eh) {
+  return (d && eh > 0) ? (size_t)rc_cemb_poff(*d, eh).total : 0;
+}
+
+size_t redcliff_cemb_workspace_bytes(const RedcliffDims* d, int32_t eh) {
+  RedcliffDims dd;
+  if (cemb_dims(d, eh, dd) != 0) return 0;
+  return sizeof(float) * (size_t)rc_cemb_ws_off(dd, eh).total * (size_t)dd.R;
+}
+
+int redcliff_cemb_workspace_regions(const RedcliffDims* d, int32_t eh, int64_t* out, int32_t n_pairs) {
+  RedcliffDims dd;
+  if (cemb_dims(d, eh, dd) != 0) return REDCLIFF_EINVAL;
+  int64_t ext[2 * RC_WS_MAX_REGIONS];
+  int nr = 0;
+  const CEmbWsOff o = rc_cemb_ws_off(dd, eh, ext, &nr);
+  for (int i = 0; i < nr && i < n_pairs; ++i) {
+    out[2 * i] = ext[2 * i];
+    out[2 * i + 1] = ext[2 * i + 1];
+  }
+  if (nr < n_pairs) {  // one more pair: (total, 0)
+    out[2 * nr] = o.total;
+    out[2 * nr + 1] = 0;
+  }
+  return nr;
+}
+
+int redcliff_cemb_train_step(const RedcliffStepArgs* a, const RedcliffCEmbArgs* ce, void* stream) {
+  if (!a || !ce) { rc_set_error("null step arguments"); return REDCLIFF_EINVAL; }
+  if (a->flags & (RC_GRAD_ONLY | RC_REFRESH_SUPPORTS)) {
+    rc_set_error("cEmbedder step: RC_GRAD_ONLY / RC_REFRESH_SUPPORTS are not supported");
+    return REDCLIFF_EINVAL;
+  }
+  RedcliffStepArgs sa = *a;
+  int e = cemb_dims(&a->d, ce->eh, sa.d);
+  if (e) return e;
+  sa.flags &= ~RC_BN_TRAIN;  // no BatchNorm in this embedder
+  sa.n_bn_updates = 0;
+  StepCtx c;
+  if ((e = make_ctx(&sa, c, true))) return e;
+  if (c.nrep == 0) return 0;
+  CEmbCtx x;
+  x.eh = ce->eh;
+  x.po = rc_cemb_poff(c.d, ce->eh);
+  x.wo = rc_cemb_ws_off(c.d, ce->eh);
+  x.ws = (float*)ce->ws;
+  x.wss = x.wo.total;
+  if (!ce->ws || ce->ws_bytes < sizeof(float) * (size_t)x.wo.total * (size_t)c.d.R) {
+    rc_set_error("cEmbedder workspace too small: %zu < %zu", ce->ws ? ce->ws_bytes : (size_t)0,
+                 sizeof(float) * (size_t)x.wo.total * (size_t)c.d.R);
+    return REDCLIFF_EWORKSPACE;
+  }
+  if (a->emb_stride < x.po.total && c.d.R > 1) { rc_set_error("cEmbedder step: emb_stride smaller than the packed group"); return REDCLIFF_EINVAL; }
+  c.cE = x.ws + x.wo.E;
+  c.cdE = x.ws + x.wo.dE;
+  c.cwss = x.wss;
+  hipStream_t s = (hipStream_t)stream;
+  const int fl = sa.flags;
+  const bool emb_grad = fl & RC_STEP_A;
+  const bool fac = (fl & (RC_STEP_B | RC_VALUES | RC_STORE_OUTPUTS)) || (emb_grad && (fl & (RC_LOSS_FORECAST | RC_LOSS_ADJ)));
+  if ((e = timed(KT_EMB_FWD, s, [&] { return rc_launch_cemb_fwd(c, x, s); }))) return e;
+  if (fac) {  // one stream: the factor chain needs w and E, the embedder backward needs its records
+    if ((e = timed(KT_EMB_FWD, s, [&] { return rc_launch_cemb_tables(c, x, s); }))) return e;
+    if ((e = timed(KT_FAC_FWD, s, [&] { return rc_launch_fac_fwd_mfma(c, s); }))) return e;
+    if ((e = timed(KT_FAC_MIX, s, [&] { return rc_launch_fac_mix(c, s); }))) return e;
+    if ((e = timed(KT_FAC_BWD, s, [&] { return rc_launch_fac_dw0(c, s); }))) return e;
+  }
+  if (fl & (RC_VALUES | RC_CONFUSION)) {
+    // k_cos_values with the symmetric E0 in place of A^T, then the head workgroup (loss values,
+    // confusion matrix): the DGCNN chain's device code, without its adjacency reduce
+    StepCtx h = c;
+    h.emb = x.ws + x.wo.E0;
+    h.es = x.wss;
+    h.eo.A = 0;
+    h.flags = fl & ~RC_STEP_A;
+    if ((fl & RC_VALUES) && (e = rc_launch_cos_values(h, s))) return e;
+    if ((e = timed(KT_EMB_BWD, s, [&] { return rc_launch_emb_bwd(h, s, false); }))) return e;
+  }
+  if (emb_grad && (e = timed(KT_EMB_FINAL, s, [&] { return rc_launch_cemb_bwd(c, x, fac, s); }))) return e;
+  return 0;
+}
+
+int redcliff_cemb_train_steps(const RedcliffStepArgs* a, const RedcliffCEmbArgs* ce, int32_t nsteps, const int64_t* rows,
+                              const int32_t* sizes, void* stream) {
+  if (!a || !ce || nsteps < 0 || (nsteps > 0 && (!rows || !sizes))) { rc_set_error("cemb_train_steps: bad arguments"); return REDCLIFF_EINVAL; }
+  RedcliffStepArgs s = *a;
+  for (int32_t i = 0; i < nsteps; ++i) {
+    s.row0 = rows[i];
+    s.B = sizes[i];
+    s.tA = a->tA + ((a->flags & RC_STEP_A) ? i : 0);
+    s.tB = a->tB + ((a->flags & RC_STEP_B) ? i : 0);
+    const int e = redcliff_cemb_train_step(&s, ce, stream);
     if (e) return e;
   }
   return 0;

@@ -220,6 +220,67 @@ inline WsOff rc_ws_off(const RedcliffDims& d, int64_t* ext = nullptr, int* next 
   return o;
 }
 
+// ---- cEmbedder chain (rc_cemb.hip) ------------------------------------------------------------
+// Offsets inside one replica's packed cEmbedder parameters: K copies of models/cmlp.py MLP
+// (Conv1d(p, eh, F) -> ReLU -> Conv1d(eh, 1, 1)), grouped by tensor; We0 columns q = c*F + t.
+struct CEmbPOff {
+  int64_t We0, be0, We1, be1, total;
+};
+inline CEmbPOff rc_cemb_poff(const RedcliffDims& d, int eh) {
+  CEmbPOff o;
+  int64_t x = 0;
+  o.We0 = x; x += (int64_t)d.K * eh * d.p * d.F;
+  o.be0 = x; x += (int64_t)d.K * eh;
+  o.We1 = x; x += (int64_t)d.K * eh;
+  o.be1 = x; x += d.K;
+  o.total = x;
+  return o;
+}
+// Offsets (floats) inside one replica's slice of the cEmbedder-private workspace.
+struct CEmbWsOff {
+  int64_t ha;    // [K][Bmax][eh]     hidden activations relu(We0 x + be0)
+  int64_t w1;    // [K][eh]           pre-update snapshot of We1
+  int64_t g;     // [K][p][F]         lagged group norms of We0 over hidden units
+  int64_t g0;    // [K][p]            lag-free group norms
+  int64_t E;     // [p][p][Ls]        fixed embedder graph, last Ls lags: sum_k g_k g_k^T
+  int64_t E0;    // [p][p]            lag-free
+  int64_t dE;    // [K][p][p][Ls]     adjacency-L1 gradient wrt E, one record per factor (k_fac_mix)
+  int64_t draw;  // [Bmax][K]         dL/d(raw embedder output)
+  int64_t total;
+};
+#define RC_CEMB_WS_REGIONS 8
+inline CEmbWsOff rc_cemb_ws_off(const RedcliffDims& d, int eh, int64_t* ext = nullptr, int* next = nullptr) {
+  CEmbWsOff o;
+  int64_t x = 0;
+  int nr = 0;
+  const int64_t G = rc_ws_guard_floats;
+  auto put = [&](int64_t& field, int64_t n) {
+    field = x;
+    if (ext && nr < RC_WS_MAX_REGIONS) { ext[2 * nr] = x; ext[2 * nr + 1] = n; }
+    ++nr;
+    x = rc_align64(x + n + G);
+  };
+  const int64_t B = d.Bmax, p = d.p, K = d.K, Ls = rc_ls(d);
+  put(o.ha, K * B * eh);
+  put(o.w1, K * eh);
+  put(o.g, K * p * d.F);
+  put(o.g0, K * p);
+  put(o.E, p * p * Ls);
+  put(o.E0, p * p);
+  put(o.dE, K * p * p * Ls);
+  put(o.draw, B * K);
+  o.total = x;
+  if (next) *next = nr;
+  return o;
+}
+// What the cEmbedder kernels need beside the StepCtx, passed by value.
+struct CEmbCtx {
+  int eh;
+  float* ws; int64_t wss;  // cEmbedder workspace, replica stride in floats
+  CEmbPOff po;
+  CEmbWsOff wo;
+};
+
 // Slots of the per-batch loss partials (after the p + K*p per-network entries).
 #define LP_FACTOR 0
 #define LP_FWL1 1
@@ -287,6 +348,12 @@ struct StepCtx {
   // the device): rc_emb_wpb(d), rc_emb_nbw(d) and the blocks of this step's B windows
   int ewpb, enbwm, enbw;
   int fzs;  // the embedder forward's fc1 slices per window (slice width mg[RC_MG_CS])
+  // cEmbedder chain (rc_cemb.hip; null / 0 in every DGCNN step): the fixed embedder graph
+  // E[p][p][Ls] that k_fac_mix's cEmbedder instantiation adds in place of A^T, the per-factor
+  // records dE[K][p][p][Ls] it writes, and the replica stride (floats) of the workspace they live in
+  const float* cE;
+  float* cdE;
+  int64_t cwss;
 };
 
 __host__ __device__ inline int rc_rep(const StepCtx& c, int i) { return c.rident ? i : (int)c.rmap[i]; }
@@ -687,3 +754,9 @@ int rc_launch_supports(const RedcliffDims& d, const float* emb, int64_t es, floa
                        WsOff wo, hipStream_t s);
 int rc_launch_bn_stats(const RedcliffDims& d, const float* X, int64_t xr, int64_t N, int B, double* st, int64_t str,
                        hipStream_t s);
+// cEmbedder chain (rc_cemb.hip): forward (+ group norms), the E / E0 tables, backward + Adam
+int rc_launch_cemb_fwd(const StepCtx& c, const CEmbCtx& e, hipStream_t s);
+int rc_launch_cemb_tables(const StepCtx& c, const CEmbCtx& e, hipStream_t s);
+int rc_launch_cemb_bwd(const StepCtx& c, const CEmbCtx& e, bool fac, hipStream_t s);
+// LDS needs of the matrix-core factor chain at Bmax windows (cemb: k_fac_mix's cEmbedder instantiation)
+bool rc_fac_mfma_fits(const RedcliffDims& d, bool cemb);

@@ -211,7 +211,12 @@ __global__ __launch_bounds__(RC_BLOCK) void k_fac_fwd_mfma(StepCtx c) {
 #ifndef RC_MIX_STAGE_U
 #define RC_MIX_STAGE_U 2
 #endif
-template <int NT>
+// CE (cEmbedder chain, rc_cemb.hip): the additive term of the conditional GC estimate is the
+// cEmbedder's fixed graph per lag, E[j][c][i] (c.cE, models/redcliff_s_cmlp_withStateSmoothing.py:
+// 500-519), instead of the DGCNN's A[c][j], and the gradient wrt it is written per lag to this
+// factor's record c.cdE[k][j][c][i] instead of summed over lags into dAadj.  CE = false is the
+// DGCNN kernel, statement for statement.
+template <int NT, bool CE = false>
 __global__ __launch_bounds__(NT) void k_fac_mix(StepCtx c, int xcd) {
   const RedcliffDims& d = c.d;
   // xcd: every network of one replica on one XCD (rc_xcd_order): the K networks of a channel
@@ -250,6 +255,7 @@ __global__ __launch_bounds__(NT) void k_fac_mix(StepCtx c, int xcd) {
   float* rA = ybuf + d.Bmax * K;  // [256]
   float* rB = rA + RC_BLOCK;      // [256]
   float* dwf = rB + RC_BLOCK;     // [Bmax]  forecast part of dL/dw_bk
+  float* Ecol = dwf + d.Bmax;     // [p*Ls]  E[j][c][i] (CE only: the launch adds the floats)
 
   RC_WG_MARK(c.ws, c.wo.total, RC_KID_FAC_MIX, 0);
   // NT < 256 (B <= 128, fac_mix_nt): the block sums run over the windows in the layout of a
@@ -350,7 +356,12 @@ __global__ __launch_bounds__(NT) void k_fac_mix(StepCtx c, int xcd) {
   // dL/dA[c][j] (-> ws.dAadj) from one sign evaluation
   const bool adj_on = adj_grad || values;
   if (adj_on) {
-    for (int cc = tid; cc < p; cc += NT) Acol[cc] = E[c.eo.A + cc * p + j];
+    if constexpr (CE) {
+      const float* Et = c.cE + r * c.cwss + (int64_t)j * p * Ls;
+      for (int e = tid; e < p * Ls; e += NT) Ecol[e] = Et[e];
+    } else {
+      for (int cc = tid; cc < p; cc += NT) Acol[cc] = E[c.eo.A + cc * p + j];
+    }
     for (int i = tid; i < Ls; i += NT) lwt[i] = logf((float)(i + 2));
     __syncthreads();
     const int half = tid & 1, hp = (p + 1) / 2, c0 = half * hp, c1 = min(p, c0 + hp);
@@ -367,12 +378,12 @@ __global__ __launch_bounds__(NT) void k_fac_mix(StepCtx c, int xcd) {
         if (b < B) {
           const float wb = wk[b];
           for (int cc = c0; cc < c1; ++cc) {  // this lane's half of the channels
-            const float ac = Acol[cc];
+            const float ac = CE ? 0.f : Acol[cc];
             const float* gr = Gs + cc * L + (L - Ls);
 #pragma unroll 4
             for (int i = 0; i < Ls; ++i) {
               const float g = gr[i];
-              const float val = wb * g + ac;
+              const float val = wb * g + (CE ? Ecol[cc * Ls + i] : ac);
               t += lwt[i] * rc_sign(val) * g;
               v += lwt[i] * fabsf(val);
             }
@@ -407,7 +418,7 @@ __global__ __launch_bounds__(NT) void k_fac_mix(StepCtx c, int xcd) {
     const bool wg = c.flags & RC_STEP_B, ag = c.flags & RC_STEP_A;
     for (int e = tid; e < p * Ls; e += NT) {
       const int cc = e / Ls, i = e - cc * Ls;
-      const float g = Gs[cc * L + (L - Ls + i)], ac = Acol[cc];
+      const float g = Gs[cc * L + (L - Ls + i)], ac = CE ? Ecol[e] : Acol[cc];
       float sw = 0.f, s1 = 0.f;
 #pragma unroll 8
       for (int b = 0; b < B; ++b) {
@@ -429,10 +440,15 @@ __global__ __launch_bounds__(NT) void k_fac_mix(StepCtx c, int xcd) {
   RC_PHASE(c.ws, c.wo.total, blockIdx.x, 21);
   if (adj_grad && (c.flags & RC_STEP_A)) {
     __syncthreads();
-    for (int cc = tid; cc < p; cc += NT) {
-      float s = 0.f;
-      for (int i = 0; i < Ls; ++i) s += dAp[cc * Ls + i];
-      ws[c.wo.dAadj + ((int64_t)k * p + cc) * p + j] = s;  // d/dA[c][j]
+    if constexpr (CE) {
+      float* dEt = c.cdE + r * c.cwss + ((int64_t)k * p + j) * p * Ls;
+      for (int e = tid; e < p * Ls; e += NT) dEt[e] = dAp[e];  // d/dE[j][c][i]
+    } else {
+      for (int cc = tid; cc < p; cc += NT) {
+        float s = 0.f;
+        for (int i = 0; i < Ls; ++i) s += dAp[cc * Ls + i];
+        ws[c.wo.dAadj + ((int64_t)k * p + cc) * p + j] = s;  // d/dA[c][j]
+      }
     }
   }
   if (!(c.flags & RC_STEP_B)) {
@@ -1365,6 +1381,15 @@ int rc_launch_fac_mix(const StepCtx& c, hipStream_t s) {
   // chains of dependent memory rounds, the same bits (every sum keeps its order: fac_mix_nt).
   // REDCLIFF_MIX_NT=256 keeps the full workgroups (A/B).
   const int nt = fac_mix_nt(d, c.B);
+  if (c.cE) {  // cEmbedder chain: + the staged E column
+    const size_t ldse = lds + sizeof(float) * (size_t)d.p * c.Ls;
+    if (ldse > RC_LDS_LIMIT_FLOATS * sizeof(float)) { rc_set_error("factor mixing: LDS budget exceeded"); return REDCLIFF_ELIMIT; }
+    if (nt == 128)
+      hipLaunchKernelGGL((k_fac_mix<128, true>), dim3(KP, c.nrep), dim3(128), ldse, s, c, (int)!(xe && xe[0] == '0'));
+    else
+      hipLaunchKernelGGL((k_fac_mix<RC_BLOCK, true>), dim3(KP, c.nrep), dim3(RC_BLOCK), ldse, s, c, (int)!(xe && xe[0] == '0'));
+    return rc_check(hipGetLastError(), "k_fac_mix (cEmbedder)");
+  }
   if (nt == 64)
     hipLaunchKernelGGL(k_fac_mix<64>, dim3(KP, c.nrep), dim3(64), lds, s, c, (int)!(xe && xe[0] == '0'));
   else if (nt == 128)
@@ -1372,6 +1397,14 @@ int rc_launch_fac_mix(const StepCtx& c, hipStream_t s) {
   else
     hipLaunchKernelGGL(k_fac_mix<RC_BLOCK>, dim3(KP, c.nrep), dim3(RC_BLOCK), lds, s, c, (int)!(xe && xe[0] == '0'));
   return rc_check(hipGetLastError(), "k_fac_mix");
+}
+
+bool rc_fac_mfma_fits(const RedcliffDims& d, bool cemb) {
+  if (fac_mix_lds(d, rc_ls(d)) + (cemb ? sizeof(float) * (size_t)d.p * rc_ls(d) : 0) > RC_LDS_LIMIT_FLOATS * sizeof(float))
+    return false;
+  const size_t cap = RC_LDS_MAX_FLOATS * sizeof(float);
+  if (rc_fac_short(d) && (ms_lds_fwd(d, d.Bmax) > cap || ms_lds_bwd(d, d.Bmax, 1) > cap)) return false;
+  return true;
 }
 
 int rc_launch_fac_dw0(const StepCtx& c, hipStream_t s) {

@@ -12,7 +12,7 @@ import torch
 _HERE = os.path.dirname(os.path.abspath(__file__))
 DEFAULT_LIB_PATH = os.path.join(_HERE, "lib", "libredcliff_hip.so")
 LIB_PATH = os.environ.get("REDCLIFF_HIP_LIB", DEFAULT_LIB_PATH)
-ABI_VERSION = 9
+ABI_VERSION = 10
 
 # RC_* step flags (include/redcliff_hip.h)
 BN_TRAIN = 1 << 0
@@ -37,7 +37,10 @@ EXPORTED = ("redcliff_abi_version", "redcliff_last_error", "redcliff_workspace_b
             "redcliff_factor_forward_workspace_floats", "redcliff_step_predictions", "redcliff_gc_norms",
             "redcliff_prox", "redcliff_kernel_timing", "redcliff_kernel_times", "redcliff_adam_apply", "redcliff_dp_update", "redcliff_gemm",
             "redcliff_gc_progress", "redcliff_gc_progress_grouped", "redcliff_debug_guard_bands", "redcliff_workspace_regions",
-            "redcliff_gc_track_stats", "redcliff_device_status", "redcliff_build_id")
+            "redcliff_gc_track_stats", "redcliff_device_status", "redcliff_build_id",
+            "redcliff_cemb_param_count", "redcliff_cemb_workspace_bytes", "redcliff_cemb_workspace_regions",
+            "redcliff_cemb_train_step", "redcliff_cemb_train_steps")
+CEMB_WS_REGIONS = ("ha", "w1", "g", "g0", "E", "E0", "dE", "draw")
 KERNEL_IDS = ("supports", "emb_fwd", "fac_fwd", "fac_bwd", "emb_bwd", "emb_final", "fac_mix", "emb_combine", "fac_lead")
 
 
@@ -75,6 +78,10 @@ class StepArgs(ctypes.Structure):
                 ("acc", _vp), ("confusion", _vp),
                 ("B_global", ctypes.c_int32), ("pad_", ctypes.c_int32), ("grad_emb", _vp), ("grad_fac", _vp),
                 ("replicas", _vp), ("n_replicas", ctypes.c_int32), ("pad2_", ctypes.c_int32)]
+
+
+class CEmbArgs(ctypes.Structure):
+    _fields_ = [("eh", ctypes.c_int32), ("pad_", ctypes.c_int32), ("ws", _vp), ("ws_bytes", ctypes.c_size_t)]
 
 
 def adam_hyper(lr, betas, eps, weight_decay):
@@ -133,10 +140,18 @@ def lib():
     L.redcliff_debug_guard_bands.argtypes = [ctypes.c_int32]
     L.redcliff_device_status.argtypes = [ctypes.POINTER(Dims), _vp, ctypes.POINTER(ctypes.c_uint32), _vp]
     L.redcliff_workspace_regions.argtypes = [ctypes.POINTER(Dims), ctypes.POINTER(_i64), ctypes.c_int32]
+    L.redcliff_cemb_param_count.argtypes = [ctypes.POINTER(Dims), ctypes.c_int32]
+    L.redcliff_cemb_workspace_bytes.argtypes = [ctypes.POINTER(Dims), ctypes.c_int32]
+    L.redcliff_cemb_workspace_regions.argtypes = [ctypes.POINTER(Dims), ctypes.c_int32, ctypes.POINTER(_i64), ctypes.c_int32]
+    L.redcliff_cemb_train_step.argtypes = [ctypes.POINTER(StepArgs), ctypes.POINTER(CEmbArgs), _vp]
+    L.redcliff_cemb_train_steps.argtypes = [ctypes.POINTER(StepArgs), ctypes.POINTER(CEmbArgs), ctypes.c_int32, _vp, _vp,
+                                            _vp]
     for name in EXPORTED[2:]:
         if name not in ("redcliff_workspace_bytes", "redcliff_emb_param_count", "redcliff_fac_param_count",
-                        "redcliff_build_id"):
+                        "redcliff_build_id", "redcliff_cemb_param_count", "redcliff_cemb_workspace_bytes"):
             getattr(L, name).restype = ctypes.c_int
+    L.redcliff_cemb_param_count.restype = ctypes.c_size_t
+    L.redcliff_cemb_workspace_bytes.restype = ctypes.c_size_t
     L.redcliff_build_id.restype = ctypes.c_char_p
     if L.redcliff_abi_version() != ABI_VERSION:
         raise ImportError("libredcliff_hip.so ABI %d != %d" % (L.redcliff_abi_version(), ABI_VERSION))
@@ -218,6 +233,16 @@ def workspace_regions(dims):
     if n < 0:
         check(n, "workspace_regions")
     return [(int(out[2 * i]), int(out[2 * i + 1])) for i in range(n)]
+
+
+def cemb_workspace_regions(dims, eh):
+    """([(start, size)] in floats of one replica's cEmbedder workspace regions, slice size)."""
+    n = len(CEMB_WS_REGIONS)
+    out = (_i64 * (2 * n + 2))()
+    got = lib().redcliff_cemb_workspace_regions(ctypes.byref(dims), int(eh), out, n + 1)
+    if got < 0:
+        check(got, "cemb_workspace_regions")
+    return [(int(out[2 * i]), int(out[2 * i + 1])) for i in range(got)], int(out[2 * got])
 
 
 def guard_bands(floats):

@@ -20,6 +20,12 @@ optimizer steps are ``redcliff_adam_apply`` (HipAdam: each group's parameters an
 are views of flat buffers, one gradient gather and one HIP launch per step).  The element-wise
 glue (bias, ReLU, BatchNorm normalisation, losses) is torch operations on the GPU tensors.
 There is no CPU path: tensors must be on the GPU and the HIP library must load.
+
+cEmbedder models inside ``cembedder_fused_supported()`` have a fused alternative for
+``batch_update`` / ``validate_training`` (and so the batch loop of ``fit()``): the kernel chain of
+csrc/rc_cemb.hip behind ``redcliff_amd.cemb_engine.CEmbEngine``, opt-in with
+``REDCLIFF_CEMB_PATH=fused``.  This path stays the default, and a fit may move between the two at
+any step.
 """
 import ctypes
 import math

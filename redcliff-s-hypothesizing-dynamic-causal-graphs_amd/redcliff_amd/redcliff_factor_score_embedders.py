@@ -4,7 +4,9 @@
 fused gfx950 kernels through the owning REDCLIFF model's FitEngine.  ``cEmbedder`` and
 the two "Vanilla" MLP classifiers keep the reference's parameter trees and seeded
 initialisation so checkpoints and seeds stay interchangeable; they run (forward, GC and
-training) on the generic HIP-GEMM path (redcliff_amd.generic).
+training) on the generic HIP-GEMM path (redcliff_amd.generic).  Training and validation steps of
+a ``cEmbedder`` model can instead run on the fused chain of csrc/rc_cemb.hip
+(``REDCLIFF_CEMB_PATH=fused``, redcliff_amd.cemb_engine).
 """
 import torch
 import torch.nn as nn
@@ -68,7 +70,9 @@ class DGCNN_Embedder(nn.Module):
 
 
 class cEmbedder(nn.Module):
-    """models/redcliff_factor_score_embedders.py:183-331."""
+    """models/redcliff_factor_score_embedders.py:183-331.  forward / GC run on the generic path;
+    the owning model's batch_update / validate_training have the fused alternative
+    (REDCLIFF_CEMB_PATH=fused, redcliff_amd.cemb_engine)."""
 
     def __init__(self, num_chans, num_class_preds, num_factor_preds, use_sigmoid_restriction,
                  sigmoid_eccentricity_coeff, lag, hidden, wavelet_level=None, save_path=None):

@@ -135,6 +135,7 @@ class REDCLIFF_S_CMLP_withStateSmoothing(nn.Module):
         st = self.__dict__.copy()
         st["_engine"] = None
         st.pop("_generic_path", None)
+        st.pop("_cemb_engine", None)
         return st
 
     def __setstate__(self, state):
@@ -155,6 +156,36 @@ class REDCLIFF_S_CMLP_withStateSmoothing(nn.Module):
                 and self.forward_pass_mode == "apply_factor_weights_after_sim_completion"
                 and self.embed_lag >= self.gen_lag
                 and self.primary_gc_est_mode == "conditional_factor_fixed_embedder")
+
+    def cembedder_fused_supported(self, Bmax=1):
+        """True when this model can train on the fused cEmbedder chain (csrc/rc_cemb.hip; opt-in with
+        REDCLIFF_CEMB_PATH=fused): cEmbedder without wavelets, num_sims == 1, one hidden layer in the
+        factors and in the embedder, factor weights applied after the simulation, embed_lag >= gen_lag,
+        conditional_factor_fixed_embedder, no Freeze training mode, and shapes inside the kernels'
+        limits for batches of up to Bmax windows (the library's own check)."""
+        from . import cemb_engine as ce
+        if not ce.static_supported(self):
+            return False
+        cache = self.__dict__.setdefault("_cemb_shape_ok", {})
+        key = int(Bmax)
+        if key not in cache:
+            cache[key] = bool(ce.shapes_supported(self, key))
+        return cache[key]
+
+    def _cemb_fused(self, Bmax):
+        """The CEmbEngine when REDCLIFF_CEMB_PATH=fused asks for it and the model (at this batch
+        size) is inside cembedder_fused_supported(); else None: the generic path runs."""
+        from . import cemb_engine as ce
+        if ce.path_requested() != "fused" or not self.cembedder_fused_supported(Bmax):
+            return None
+        W = self.factors[0].networks[0].layers[0].weight
+        if not W.is_cuda:
+            raise RuntimeError("REDCLIFF-S on MI355X: move the model to the GPU first (model.cuda()); "
+                               "there is no CPU path")
+        eng = self.__dict__.get("_cemb_engine")
+        if eng is None or eng.device != W.device:
+            eng = self.__dict__["_cemb_engine"] = ce.CEmbEngine(self)
+        return eng
 
     def check_device_status(self):
         """Raise if a merged-backward hand-off wait on the device timed out since the last check
@@ -593,6 +624,22 @@ class REDCLIFF_S_CMLP_withStateSmoothing(nn.Module):
         if output_length != 1:
             raise NotImplementedError("output_length must be 1 (num_sims * output_length target steps)")
         kinds = phase_of_epoch(self, epoch_num)
+        ceng = None if self.fused_supported() else self._cemb_fused(X.shape[0])
+        if ceng is not None:  # the fused cEmbedder chain (REDCLIFF_CEMB_PATH=fused)
+            Xd, lab, d = ceng.stage(X, Y)
+            if running_factor_score_confusion_matrix is not None:
+                ceng.conf.zero_()
+            ceng.run_steps(kinds, Xd, lab, d, [0], [Xd.shape[0]], optimizerA, optimizerB)
+            gp = self.__dict__.get("_generic_path")
+            if gp is not None:  # the engine's moments and step counts are the optimizers' state now
+                for g, opt in (("A", optimizerA), ("B", optimizerB)):
+                    if ceng.opt[g] is not None and ceng.opt[g]["opt"] is opt:
+                        gp._adams.pop(id(opt), None)
+            self._set_module_modes(kinds[-1] if kinds else None)
+            if running_factor_score_confusion_matrix is not None and self.num_supervised_factors > 0:
+                n = self.num_supervised_factors
+                running_factor_score_confusion_matrix += ceng.conf.cpu().numpy().reshape(n, n)
+            return best_model, running_factor_score_confusion_matrix
         if not self.fused_supported():
             dev = self._device()
             n = self.num_supervised_factors
@@ -627,6 +674,20 @@ class REDCLIFF_S_CMLP_withStateSmoothing(nn.Module):
                           factor_score_val_tpr_history=None, factor_score_val_tnr_history=None,
                           factor_score_val_fpr_history=None, factor_score_val_fnr_history=None):
         """...withStateSmoothing.py:1650-1790: coefficient-normalised loss terms averaged over batches."""
+        ceng = None
+        if not self.fused_supported() and output_length == 1:
+            sizes = [int(Xb.shape[0]) for Xb, _ in X_val]
+            ceng = self._cemb_fused(max(sizes)) if sizes else None
+        if ceng is not None:  # the fused cEmbedder chain (REDCLIFF_CEMB_PATH=fused)
+            self.factor_score_embedder.eval()
+            for f in self.factors:
+                f.eval()
+            ds = ceng.cache_dataset(X_val)
+            d = ceng.workspace(ds["Bmax"], ds["T"])
+            acc, conf = ceng.run_values(ds["X"], ds["lab"], d, ds["rows"], ds["sizes"])
+            return self._validation_tuple(acc, float(ds["len"]), conf, factor_score_val_acc_history,
+                                          factor_score_val_tpr_history, factor_score_val_tnr_history,
+                                          factor_score_val_fpr_history, factor_score_val_fnr_history)
         if not self.fused_supported():
             for f in self.factors:
                 f.eval()
