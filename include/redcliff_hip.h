@@ -332,10 +332,50 @@ int redcliff_cemb_train_step(const RedcliffStepArgs* a, const RedcliffCEmbArgs* 
 int redcliff_cemb_train_steps(const RedcliffStepArgs* a, const RedcliffCEmbArgs* e, int32_t nsteps,
                               const int64_t* rows, const int32_t* sizes, void* stream);
 
+/* ---- scoring whole recordings (general_utils/misc.py:57-81, evaluate/eval_utils.py:953-1087) ----
+ * Purely additive entries: REDCLIFF_ABI_VERSION stays 10, no existing entry or layout changes.
+ *
+ * The DGCNN factor-score embedder in inference mode (BatchNorm running statistics) over sliding
+ * windows of Nrec recordings X[r][T][p] (fp32, rows contiguous, x_rstride floats between
+ * recordings): scored step j < count uses rows [start + j*stride - F, start + j*stride) as a
+ * time-major window; the windows are never materialised.  Outputs, contiguous:
+ *   w[r][j][K]         factor weightings (sigmoid(ecc * raw) under the sigmoid restriction, else raw)
+ *   logits[r][j][nsup] class scores raw[:nsup] (sigmoid(raw) when the restriction is on and
+ *                      use_final_activation != 0); may be NULL when nsup == 0
+ *   graphs[r][j][Q]    optional graph trace bias[q] + sum_k w[r][j][k] tab[k][q] (k ascending) from
+ *                      the caller's tab[K][Q] and bias[Q] (bias may be NULL): the conditional graph of
+ *                      every scored step (...withStateSmoothing.py:481-498, :565-580) summed over factors
+ * emb is the packed embedder block (layout above), bn_rm / bn_rv the running statistics [F]; the
+ * call reads them only.  ws: redcliff_score_recording_workspace_bytes(d) bytes, private to the call
+ * (supports and folded BatchNorm tables of the current parameters, rebuilt by every call).
+ * Of RedcliffDims only p, K, F, n, H, M1, nsup, use_sigmoid and sigmoid_ecc are read.  Limits:
+ * p <= 64, F <= 64, n <= 4, M1 <= 64, K <= 16, p*H, M1*H, F*H <= 8192 and n*p*(F + 15) + n*F*H + 1088
+ * <= 40960 floats of LDS; outside them REDCLIFF_ELIMIT (the size query returns 0).  start < F,
+ * stride < 1, count < 0, a last window that ends past T and null buffers give REDCLIFF_EINVAL;
+ * count == 0 launches nothing.  Stream-ordered, no host synchronisation, no atomics: the same
+ * arguments give the same bits, and a window's results do not depend on count, stride, Nrec or on
+ * its position in the launch. */
+typedef struct RedcliffScoreArgs {
+  RedcliffDims d;
+  const float* emb; const float* bn_rm; const float* bn_rv;
+  double bn_eps;                         /* BatchNorm1d.eps                                   */
+  const float* X; int64_t x_rstride;
+  int32_t Nrec, T;
+  int32_t start, count, stride;
+  int32_t use_final_activation;
+  float* w; float* logits;
+  const float* tab; const float* bias; float* graphs;  /* graphs == NULL: no graph trace        */
+  int32_t Q; int32_t pad_;
+  void* ws; size_t ws_bytes;
+} RedcliffScoreArgs;
+size_t redcliff_score_recording_workspace_bytes(const RedcliffDims* d);
+int redcliff_score_recording(const RedcliffScoreArgs* a, void* stream);
+
 /* Per-kernel HIP-event timing for benchmarking: redcliff_kernel_timing(1) brackets every
  * kernel launched by redcliff_train_step with events on its stream; redcliff_kernel_times()
- * synchronises them and returns per-kernel totals (ids 0..7: supports, emb_fwd, fac_fwd,
- * fac_bwd, emb_bwd, emb_final, fac_mix, emb_combine, fac_lead).  Returns the number of kernel ids.
+ * synchronises them and returns per-kernel totals (ids 0..10: supports, emb_fwd, fac_fwd,
+ * fac_bwd, emb_bwd, emb_final, fac_mix, emb_combine, fac_lead, and redcliff_score_recording's
+ * score, score_graphs).  Returns the number of kernel ids.
  * When a single fit (R == 1) splits into two kernel chains (GEMM-shaped embedder and / or
  * matrix-core factor path), the factor chain runs on an internal second stream (one per host
  * thread and device) forked from and joined back into `stream` with events, so stream

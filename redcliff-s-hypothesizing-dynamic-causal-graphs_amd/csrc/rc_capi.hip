@@ -9,7 +9,7 @@
 
 // ---- optional per-kernel HIP-event timing (bench / profiling only) -------------------------
 namespace {
-enum { KT_SUPPORTS = 0, KT_EMB_FWD, KT_FAC_FWD, KT_FAC_BWD, KT_EMB_BWD, KT_EMB_FINAL, KT_FAC_MIX, KT_EMB_COMB, KT_FAC_LEAD, KT_N };
+enum { KT_SUPPORTS = 0, KT_EMB_FWD, KT_FAC_FWD, KT_FAC_BWD, KT_EMB_BWD, KT_EMB_FINAL, KT_FAC_MIX, KT_EMB_COMB, KT_FAC_LEAD, KT_SCORE, KT_SCORE_GRAPHS, KT_N };
 struct TimedLaunch {
   int id;
   hipEvent_t a, b;
@@ -626,10 +626,104 @@ int redcliff_cemb_train_steps(const RedcliffStepArgs* a, const RedcliffCEmbArgs*
   return 0;
 }
 
+// ---- recording scoring (rc_score.hip) -----------------------------------------------------------
+// The embedder-side limits of check_dims (Bmax, T and the factor dimensions play no part) plus the
+// window kernel's LDS budget.
+static int score_dims(const RedcliffDims* d) {
+  if (!d) { rc_set_error("null dims"); return REDCLIFF_EINVAL; }
+  if (d->p < 1 || d->K < 1 || d->F < 1 || d->n < 1 || d->H < 1 || d->M1 < 1 || d->nsup < 0 || d->nsup > d->K) {
+    rc_set_error("invalid dims (p=%d K=%d F=%d n=%d H=%d M1=%d nsup=%d)", d->p, d->K, d->F, d->n, d->H, d->M1, d->nsup);
+    return REDCLIFF_EINVAL;
+  }
+  if (d->p > 64 || d->K > 16 || d->F > 64 || d->n > 4 || d->M1 > 64 || d->p * d->H > 32 * RC_BLOCK ||
+      d->M1 * d->H > 32 * RC_BLOCK || d->F * d->H > 32 * RC_BLOCK) {
+    rc_set_error("dims outside kernel limits (p<=64 K<=16 F<=64 n<=4 M1<=64 p*H,M1*H,F*H<=8192)");
+    return REDCLIFF_ELIMIT;
+  }
+  if (rc_score_rows_budget(*d) <= 0) {
+    rc_set_error("dims outside kernel limits (score_recording LDS budget: n*p*(F+15) + n*F*H floats)");
+    return REDCLIFF_ELIMIT;
+  }
+  return 0;
+}
+
+struct ScoreWs {
+  int64_t S, Wf, Zb, total;
+};
+static ScoreWs score_ws(const RedcliffDims& d) {
+  ScoreWs o;
+  int64_t x = 0;
+  o.S = x; x = rc_align64(x + (int64_t)d.n * d.p * d.p);
+  o.Wf = x; x = rc_align64(x + (int64_t)d.n * d.F * d.H);
+  o.Zb = x; x = rc_align64(x + (int64_t)d.p * d.H);
+  o.total = x;
+  return o;
+}
+
+size_t redcliff_score_recording_workspace_bytes(const RedcliffDims* d) {
+  if (score_dims(d) != 0) return 0;
+  return sizeof(float) * (size_t)score_ws(*d).total;
+}
+
+int redcliff_score_recording(const RedcliffScoreArgs* a, void* stream) {
+  if (!a) { rc_set_error("null score arguments"); return REDCLIFF_EINVAL; }
+  int e = score_dims(&a->d);
+  if (e) return e;
+  const RedcliffDims& d = a->d;
+  if (!a->emb || !a->bn_rm || !a->bn_rv || !a->X || !a->w || !a->ws || (d.nsup > 0 && !a->logits) ||
+      (a->graphs && !a->tab)) {
+    rc_set_error("score_recording: null buffer in arguments");
+    return REDCLIFF_EINVAL;
+  }
+  if (a->Nrec < 1 || a->T < 1 || a->x_rstride < 0 || a->start < d.F || a->stride < 1 || a->count < 0 ||
+      (a->graphs && a->Q < 1)) {
+    rc_set_error("score_recording: bad arguments (Nrec=%d T=%d start=%d (>= F=%d) stride=%d count=%d Q=%d)", a->Nrec, a->T,
+                 a->start, d.F, a->stride, a->count, a->Q);
+    return REDCLIFF_EINVAL;
+  }
+  if (a->count > 0 && (int64_t)a->start + (int64_t)(a->count - 1) * a->stride > (int64_t)a->T) {
+    rc_set_error("score_recording: the last window ends at row %lld, past T=%d",
+                 (long long)a->start + (long long)(a->count - 1) * a->stride, a->T);
+    return REDCLIFF_EINVAL;
+  }
+  const ScoreWs o = score_ws(d);
+  if (a->ws_bytes < sizeof(float) * (size_t)o.total) {
+    rc_set_error("score_recording: workspace too small: %zu < %zu", a->ws_bytes, sizeof(float) * (size_t)o.total);
+    return REDCLIFF_EWORKSPACE;
+  }
+  if (a->count == 0) return 0;
+  hipStream_t s = (hipStream_t)stream;
+  float* ws = (float*)a->ws;
+  const EmbOff eo = rc_emb_off(d);
+  // the supports of this call's A in this call's workspace (k_supports with the S region placed there)
+  RedcliffDims d1 = d;
+  d1.R = 1;
+  WsOff wo;
+  memset(&wo, 0, sizeof(wo));
+  wo.S = o.S;
+  if ((e = timed(KT_SUPPORTS, s, [&] { return rc_launch_supports(d1, a->emb, 0, ws, 0, eo, wo, s); }))) return e;
+  if ((e = timed(KT_SUPPORTS, s, [&] {
+         return rc_launch_score_tables(d, eo, a->emb, a->bn_rm, a->bn_rv, (float)a->bn_eps, ws + o.S, ws + o.Wf, ws + o.Zb, s);
+       })))
+    return e;
+  if ((e = timed(KT_SCORE, s, [&] {
+         return rc_launch_score_windows(d, eo, a->emb, a->X, a->x_rstride, a->Nrec, a->start, a->count, a->stride,
+                                        a->use_final_activation, ws + o.S, ws + o.Wf, ws + o.Zb, a->w, a->logits, s);
+       })))
+    return e;
+  if (a->graphs &&
+      (e = timed(KT_SCORE_GRAPHS, s, [&] {
+         return rc_launch_score_graphs(a->w, a->tab, a->bias, a->graphs, d.K, a->Q, (int64_t)a->Nrec * a->count, s);
+       })))
+    return e;
+  return 0;
+}
+
 // Per-kernel timing: while enabled every launch of redcliff_train_step is bracketed by
 // HIP events on its stream.  redcliff_kernel_times() waits for the recorded events,
 // adds the elapsed milliseconds per kernel (ids: supports, emb_fwd, fac_fwd, fac_bwd,
-// emb_bwd, emb_final, fac_mix, emb_combine, fac_lead) into total_ms[]/counts[] and clears the record.
+// emb_bwd, emb_final, fac_mix, emb_combine, fac_lead, score, score_graphs) into total_ms[]/counts[] and
+// clears the record.
 int redcliff_kernel_timing(int32_t enable) {
   g_timing = enable != 0;
   return 0;

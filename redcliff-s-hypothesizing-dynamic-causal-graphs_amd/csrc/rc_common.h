@@ -760,3 +760,13 @@ int rc_launch_cemb_tables(const StepCtx& c, const CEmbCtx& e, hipStream_t s);
 int rc_launch_cemb_bwd(const StepCtx& c, const CEmbCtx& e, bool fac, hipStream_t s);
 // LDS needs of the matrix-core factor chain at Bmax windows (cemb: k_fac_mix's cEmbedder instantiation)
 bool rc_fac_mfma_fits(const RedcliffDims& d, bool cemb);
+// recording scoring (rc_score.hip): the LDS rows per (support, channel) a tile may stage (0: the
+// shape does not fit), the folded tables, the sliding-window embedder, the graph trace
+int rc_score_rows_budget(const RedcliffDims& d);
+int rc_launch_score_tables(const RedcliffDims& d, const EmbOff& eo, const float* emb, const float* rm, const float* rv,
+                           float bn_eps, const float* S, float* Wf, float* Zb, hipStream_t s);
+int rc_launch_score_windows(const RedcliffDims& d, const EmbOff& eo, const float* emb, const float* X, int64_t xrs,
+                            int Nrec, int start, int count, int stride, int ufa, const float* S, const float* Wf,
+                            const float* Zb, float* w, float* logits, hipStream_t s);
+int rc_launch_score_graphs(const float* w, const float* tab, const float* bias, float* out, int K, int Q, int64_t nwin,
+                           hipStream_t s);

@@ -39,9 +39,11 @@ EXPORTED = ("redcliff_abi_version", "redcliff_last_error", "redcliff_workspace_b
             "redcliff_gc_progress", "redcliff_gc_progress_grouped", "redcliff_debug_guard_bands", "redcliff_workspace_regions",
             "redcliff_gc_track_stats", "redcliff_device_status", "redcliff_build_id",
             "redcliff_cemb_param_count", "redcliff_cemb_workspace_bytes", "redcliff_cemb_workspace_regions",
-            "redcliff_cemb_train_step", "redcliff_cemb_train_steps")
+            "redcliff_cemb_train_step", "redcliff_cemb_train_steps",
+            "redcliff_score_recording_workspace_bytes", "redcliff_score_recording")
 CEMB_WS_REGIONS = ("ha", "w1", "g", "g0", "E", "E0", "dE", "draw")
-KERNEL_IDS = ("supports", "emb_fwd", "fac_fwd", "fac_bwd", "emb_bwd", "emb_final", "fac_mix", "emb_combine", "fac_lead")
+KERNEL_IDS = ("supports", "emb_fwd", "fac_fwd", "fac_bwd", "emb_bwd", "emb_final", "fac_mix", "emb_combine", "fac_lead",
+              "score", "score_graphs")
 
 
 class Dims(ctypes.Structure):
@@ -82,6 +84,16 @@ class StepArgs(ctypes.Structure):
 
 class CEmbArgs(ctypes.Structure):
     _fields_ = [("eh", ctypes.c_int32), ("pad_", ctypes.c_int32), ("ws", _vp), ("ws_bytes", ctypes.c_size_t)]
+
+
+class ScoreArgs(ctypes.Structure):
+    """RedcliffScoreArgs (redcliff_score_recording)."""
+    _fields_ = [("d", Dims), ("emb", _vp), ("bn_rm", _vp), ("bn_rv", _vp), ("bn_eps", ctypes.c_double),
+                ("X", _vp), ("x_rstride", _i64), ("Nrec", ctypes.c_int32), ("T", ctypes.c_int32),
+                ("start", ctypes.c_int32), ("count", ctypes.c_int32), ("stride", ctypes.c_int32),
+                ("use_final_activation", ctypes.c_int32), ("w", _vp), ("logits", _vp),
+                ("tab", _vp), ("bias", _vp), ("graphs", _vp), ("Q", ctypes.c_int32), ("pad_", ctypes.c_int32),
+                ("ws", _vp), ("ws_bytes", ctypes.c_size_t)]
 
 
 def adam_hyper(lr, betas, eps, weight_decay):
@@ -146,12 +158,16 @@ def lib():
     L.redcliff_cemb_train_step.argtypes = [ctypes.POINTER(StepArgs), ctypes.POINTER(CEmbArgs), _vp]
     L.redcliff_cemb_train_steps.argtypes = [ctypes.POINTER(StepArgs), ctypes.POINTER(CEmbArgs), ctypes.c_int32, _vp, _vp,
                                             _vp]
+    L.redcliff_score_recording_workspace_bytes.argtypes = [ctypes.POINTER(Dims)]
+    L.redcliff_score_recording.argtypes = [ctypes.POINTER(ScoreArgs), _vp]
     for name in EXPORTED[2:]:
         if name not in ("redcliff_workspace_bytes", "redcliff_emb_param_count", "redcliff_fac_param_count",
-                        "redcliff_build_id", "redcliff_cemb_param_count", "redcliff_cemb_workspace_bytes"):
+                        "redcliff_build_id", "redcliff_cemb_param_count", "redcliff_cemb_workspace_bytes",
+                        "redcliff_score_recording_workspace_bytes"):
             getattr(L, name).restype = ctypes.c_int
     L.redcliff_cemb_param_count.restype = ctypes.c_size_t
     L.redcliff_cemb_workspace_bytes.restype = ctypes.c_size_t
+    L.redcliff_score_recording_workspace_bytes.restype = ctypes.c_size_t
     L.redcliff_build_id.restype = ctypes.c_char_p
     if L.redcliff_abi_version() != ABI_VERSION:
         raise ImportError("libredcliff_hip.so ABI %d != %d" % (L.redcliff_abi_version(), ABI_VERSION))

@@ -382,3 +382,44 @@ def batched_graph_f1(est_stack, true_stack, normalize=True, lag_sum=True, exclud
     auc = batched_roc_auc(E.reshape(E.shape[0], -1), labels.reshape(E.shape[0], -1))
     graphs = (E >= thr[:, None, None]).astype(np.int64)
     return dict(f1=f1, threshold=thr, roc_auc=auc, graphs=graphs)
+
+
+# ----------------------------------------------------------------------------------------
+# factor scores across a recording (general_utils/misc.py:57-81; evaluate/eval_utils.py:953-1087)
+# ----------------------------------------------------------------------------------------
+def _scores_across_recording(model, recorded_signal, num_supervised_factors, num_timesteps_to_score,
+                             num_timesteps_in_input_history, which):
+    """which: 0 = factor weightings, 1 = class predictions (the embedder's two return values)."""
+    assert recorded_signal.shape[0] == 1
+    hist, num = num_timesteps_in_input_history, num_timesteps_to_score
+    assert recorded_signal.shape[1] >= num + hist
+    weightings = np.zeros((num_supervised_factors, num))
+    emb = model.factor_score_embedder
+    # One device call for the whole recording when it computes what the loop below computes: the
+    # embedder in eval mode (in training mode the reference's BatchNorm uses batch statistics and
+    # updates the running ones at every step), windows of embed_lag steps, and p != F (at p == F
+    # DGCNN_Embedder.forward reads the window untransposed, models/redcliff_factor_score_embedders.py:369-371)
+    if (hasattr(model, "score_recording") and not emb.training and hist == getattr(model, "embed_lag", None)
+            and recorded_signal.shape[2] != hist and (which == 0 or getattr(model, "num_supervised_factors", 0) > 0)):
+        res = model.score_recording(recorded_signal[0], start=hist, count=num, stride=1)
+        vals = res.w if which == 0 else res.logits
+        return weightings + vals[0, :, :num_supervised_factors].detach().cpu().numpy().T
+    for i in range(hist, hist + num):
+        out = emb(recorded_signal[:, i - hist:i, :])[which]
+        weightings[:, i - hist] = weightings[:, i - hist] + out[0, :num_supervised_factors].detach().cpu().numpy()
+    return weightings
+
+
+def obtain_factor_score_weightings_across_recording(model, recorded_signal, num_supervised_factors,
+                                                    num_timesteps_to_score, num_timesteps_in_input_history):
+    """general_utils/misc.py:57-68 -- float64 (num_supervised_factors, num_timesteps_to_score) factor
+    weightings of recorded_signal (1, T >= scored steps + history, num_channels)."""
+    return _scores_across_recording(model, recorded_signal, num_supervised_factors, num_timesteps_to_score,
+                                    num_timesteps_in_input_history, 0)
+
+
+def obtain_factor_score_classifications_across_recording(model, recorded_signal, num_supervised_factors,
+                                                         num_timesteps_to_score, num_timesteps_in_input_history):
+    """general_utils/misc.py:70-81 -- the same for the embedder's class predictions."""
+    return _scores_across_recording(model, recorded_signal, num_supervised_factors, num_timesteps_to_score,
+                                    num_timesteps_in_input_history, 1)

@@ -287,6 +287,22 @@ class REDCLIFF_S_CMLP_withStateSmoothing(nn.Module):
         preds = [y[:, k, :].unsqueeze(1) for k in range(self.num_factors_nK)]
         return xs.unsqueeze(1), preds, [w], [logits for _ in range(self.num_sims)]
 
+    def score_recording(self, X, start=None, count=None, stride=1, use_final_activation=True, graphs=None,
+                        gc_est_mode=None, ignore_lag=True):
+        """Factor scores of every scored step of recordings X (T, p) or (Nrec, T, p) in one call (the
+        reference scores a recording one embedder call per step, general_utils/misc.py:57-81): step j
+        uses rows [start + j*stride - embed_lag, start + j*stride) as a time-major window; defaults
+        start = embed_lag and every step that fits.  Inference semantics, no module state changes.
+        Returns scoring.RecordingScores: w (Nrec, count, K), logits (Nrec, count, nsup) | None and,
+        with graphs="sum", graphs (Nrec, count, p, p, L') whose entry [r, j] equals
+        sum(self.GC(mode, X=window, threshold=False, ignore_lag=ignore_lag)[0]) for
+        mode = gc_est_mode or primary_gc_est_mode (conditional_factor_exclusive /
+        conditional_factor_fixed_embedder).  Fused kernel (csrc/rc_score.hip) for DGCNN models inside
+        fused_supported() without wavelets; every other model runs the chunked route."""
+        from . import scoring
+        return scoring.score_recording(self, X, start, count, stride, use_final_activation, graphs, gc_est_mode,
+                                       ignore_lag)
+
     # ------------------------------------------------------------------ GC
     def _factor_gcs(self, threshold, ignore_lag, combine=False, rank=False):
         """cMLP.GC of every factor (models/cmlp.py:147-203: norms, wavelet ranking / combination,
