@@ -7,6 +7,7 @@ or does not export the expected ABI, so a broken build fails loudly.
 import ctypes
 import os
 
+import numpy as np
 import torch
 
 _HERE = os.path.dirname(os.path.abspath(__file__))
@@ -204,6 +205,21 @@ def check(rc, what=""):
         raise RuntimeError("redcliff HIP call %s failed (%d): %s" % (what, rc, msg))
 
 
+def train_steps(a, rows, sizes, stream, what, bn_step=0, cemb=None):
+    """One launch chain over consecutive batches: batch i is `sizes[i]` windows from row `rows[i]`,
+    its BatchNorm statistics `bn_step` doubles after batch i-1's.  redcliff_train_steps, or with
+    `cemb` (a CEmbArgs) redcliff_cemb_train_steps; returns the number of batches."""
+    rows = np.ascontiguousarray(rows, dtype=np.int64)
+    sizes = np.ascontiguousarray(sizes, dtype=np.int32)
+    rp, sp = rows.ctypes.data_as(_vp), sizes.ctypes.data_as(_vp)
+    if cemb is None:
+        rc = lib().redcliff_train_steps(ctypes.byref(a), len(rows), rp, sp, bn_step, stream)
+    else:
+        rc = lib().redcliff_cemb_train_steps(ctypes.byref(a), ctypes.byref(cemb), len(rows), rp, sp, stream)
+    check(rc, what)
+    return len(rows)
+
+
 def workspace_layout(dims):
     out = (_i64 * len(WS_REGIONS))()
     n = lib().redcliff_workspace_layout(ctypes.byref(dims), out, len(WS_REGIONS))
@@ -221,7 +237,6 @@ def raise_on_status(words, view=None, where="step"):
     """words: host copy of status_view (or redcliff_device_status's output).  Non-zero = a merged
     backward consumer stopped waiting for its producers (rc_wait_count ran out of polls), so the
     steps since the last check computed gradients from unwritten records: clear and raise."""
-    import numpy as np
     w = np.asarray(words).reshape(-1)
     bad = np.nonzero(w)[0]
     if bad.size:

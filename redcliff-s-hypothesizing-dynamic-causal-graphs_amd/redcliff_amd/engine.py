@@ -1,6 +1,6 @@
 """Device state of a REDCLIFF-S fit and the fused gfx950 training step.
 
-``FitEngine`` owns, per model:
+``PackedEngine`` owns, per model, what every fused fit shares:
   * the packed parameter buffers (embedder group A, factor group B).  Every nn.Parameter
     of the model is re-pointed to a view of these buffers, so ``state_dict()``, the
     user's optimizers and the kernels all see the same memory;
@@ -9,6 +9,10 @@
   * the workspace of the kernel chain and the device-resident copy of the training set
     (the reference re-reads and re-unpickles its data for every item,
     data/synthetic_datasets.py:135-244; here the windows are uploaded once).
+
+``FitEngine`` is the DGCNN fit: the embedder layout, the BatchNorm buffers and batch statistics,
+the Chebyshev supports' freshness, the workspace status word, prepared epochs (``StepPlan``) and
+the forward-only launches.  ``cemb_engine.CEmbEngine`` is the cEmbedder fit.
 
 One ``batch_update`` of the reference (models/redcliff_s_cmlp_withStateSmoothing.py:734-933)
 is one ``redcliff_train_step`` call; an epoch is one ``redcliff_train_steps`` call.
@@ -23,6 +27,7 @@ from .dgcnn import M1
 from .kernels import factor_views, ptr
 
 BMAX_LIMIT = 512  # windows per launch (include/redcliff_hip.h: Bmax <= 512)
+_ROW0 = np.zeros(1, dtype=np.int64)  # the rows of a one-batch dataset
 
 
 # ----------------------------------------------------------------------------- phases
@@ -84,79 +89,51 @@ def select_labels(Y, K, Lmax):
     return lab[:, :K].contiguous()
 
 
-# ----------------------------------------------------------------------------- engine
-class FitEngine:
-    def __init__(self, model):
+# ----------------------------------------------------------------------------- engines
+class PackedEngine:
+    """What the fused fits share, whatever the factor-score embedder.  A subclass supplies the
+    embedder group (``_emb_layout``, ``_emb_pairs``, ``_lib_emb_params``), its ``dims`` and its
+    step launches (``run_steps`` / ``run_values``), and sets what its own methods read before it
+    calls ``__init__`` here, which ends by binding the parameters."""
+
+    WS_ERROR = (-1, "workspace_bytes")  # what workspace() reports for shapes outside the kernels' limits
+
+    def __init__(self, model, F, device):
         self.model = model
         emb = model.factor_score_embedder
-        self.dgcnn = emb.dgcnn.dgcnn
         self.p = model.num_series
         self.L = model.gen_lag
         self.K = model.num_factors_nK
         self.nsup = model.num_supervised_factors
         self.h = model.gen_hidden[0]
-        self.F = self.dgcnn.in_channels
-        self.n = self.dgcnn.num_layers
-        self.H = self.dgcnn.hid_channels
+        self.F = F
         self.Lmax = max(model.gen_lag, model.embed_lag)
-        self.device = self.dgcnn.A.device
+        self.device = device
         self.sig = bool(emb.use_sigmoid_restriction)
         self.ecc = float(emb.sigmoid_eccentricity_coeff or 0.0)
-        self._emb_layout()
-        PA = self.eo["total"]
-        PB = self.fo["total"]
-        dev = self.device
-        self.emb = torch.empty(PA, device=dev, dtype=torch.float32)
-        self.fac = torch.empty(PB, device=dev, dtype=torch.float32)
-        self.bn = torch.empty(2, self.F, device=dev, dtype=torch.float32)
-        self.acc = torch.zeros(8, device=dev, dtype=torch.float64)
-        self.conf = torch.zeros(max(self.nsup, 1) ** 2, device=dev, dtype=torch.int32)
-        self.opt = {"A": None, "B": None}  # bound optimizer state per group
-        self.ws = None
-        self.ws_dims = None
-        self.hyper_key = None
-        self.hyper_dev = None
-        self.supports_fresh = False
-        self._a_version = -1
-        self.dataset_cache = {}
-        self.pack = None  # ReplicaPack this fit belongs to (redcliff_amd.replicas), if any
-        self.pack_index = None
-        self.bind()
-
-    # ------------------------------------------------------------------ layout / binding
-    def _emb_layout(self):
-        p, n, F, H, K = self.p, self.n, self.F, self.H, self.K
-        o = {"A": 0}
-        o["gcW"] = o["A"] + p * p
-        o["bnw"] = o["gcW"] + n * F * H
-        o["bnb"] = o["bnw"] + F
-        o["fc1W"] = o["bnb"] + F
-        o["fc1b"] = o["fc1W"] + M1 * p * H
-        o["fc2W"] = o["fc1b"] + M1
-        o["fc2b"] = o["fc2W"] + K * M1
-        o["total"] = o["fc2b"] + K
-        self.eo = o
-        kp = K * self.p
+        self.eo = self._emb_layout()
+        kp = self.K * self.p
         fo = {"W0": 0}
         fo["b0"] = fo["W0"] + kp * self.h * self.p * self.L
         fo["W1"] = fo["b0"] + kp * self.h
         fo["b1"] = fo["W1"] + kp * self.h
         fo["total"] = fo["b1"] + kp
         self.fo = fo
+        self.emb = torch.empty(self.eo["total"], device=device, dtype=torch.float32)
+        self.fac = torch.empty(fo["total"], device=device, dtype=torch.float32)
+        self.acc = torch.zeros(8, device=device, dtype=torch.float64)
+        self.conf = torch.zeros(max(self.nsup, 1) ** 2, device=device, dtype=torch.int32)
+        self.opt = {"A": None, "B": None}  # bound optimizer state per group
+        self.ws = None
+        self.ws_dims = None
+        self.hyper_key = None
+        self.hyper_dev = None
+        self.dataset_cache = {}
+        self.pack = None  # ReplicaPack this fit belongs to (redcliff_amd.replicas), if any
+        self.pack_index = None
+        self.bind()
 
-    def _emb_pairs(self):
-        g, o, E = self.dgcnn, self.eo, self.emb
-        p, n, F, H, K = self.p, self.n, self.F, self.H, self.K
-        pairs = [(g.A, E[o["A"]:o["A"] + p * p].view(p, p))]
-        for i in range(n):
-            pairs.append((g.layer1.gc1[i].weight, E[o["gcW"] + i * F * H:o["gcW"] + (i + 1) * F * H].view(F, H)))
-        pairs += [(g.BN1.weight, E[o["bnw"]:o["bnw"] + F]), (g.BN1.bias, E[o["bnb"]:o["bnb"] + F]),
-                  (g.fc1.linear.weight, E[o["fc1W"]:o["fc1W"] + M1 * p * H].view(M1, p * H)),
-                  (g.fc1.linear.bias, E[o["fc1b"]:o["fc1b"] + M1]),
-                  (g.fc2.linear.weight, E[o["fc2W"]:o["fc2W"] + K * M1].view(K, M1)),
-                  (g.fc2.linear.bias, E[o["fc2b"]:o["fc2b"] + K])]
-        return pairs
-
+    # ------------------------------------------------------------------ layout / binding
     def _fac_pairs(self):
         return factor_views(self.fac, list(self.model.factors), self.p, self.h, self.L)
 
@@ -164,40 +141,25 @@ class FitEngine:
         """Copy current parameter values into the packed buffers and alias the parameters.
         copy=False: the buffers already hold the values (attach_pack moved them in bulk)."""
         with torch.no_grad():
-            self.pairs = self._emb_pairs() + self._fac_pairs()
+            emb_pairs = self._emb_pairs()
+            self.pairs = emb_pairs + self._fac_pairs()
+            params = [prm for prm, _ in self.pairs]  # group A: the embedder's, first; group B: the factors'
+            self.group_params = {"A": params[:len(emb_pairs)], "B": params[len(emb_pairs):]}
             if copy:  # one multi-tensor launch instead of a copy kernel per parameter
                 views = [view for _, view in self.pairs]
                 srcs = [prm.detach().to(view.device).reshape(view.shape) for prm, view in self.pairs]
                 torch._foreach_copy_(views, srcs)
             for prm, view in self.pairs:
                 prm.data = view
-            bnm = self.dgcnn.BN1
-            self.bn[0].copy_(bnm.running_mean)
-            self.bn[1].copy_(bnm.running_var)
-            bnm.running_mean = self.bn[0]
-            bnm.running_var = self.bn[1]
         self.bound_ptrs = [prm.data_ptr() for prm, _ in self.pairs]
-        self.supports_fresh = False
 
-    def ensure_bound(self):
-        cur = [prm.data_ptr() for prm, _ in self.pairs]
-        bn = self.dgcnn.BN1
-        if (cur != self.bound_ptrs or bn.running_mean.data_ptr() != self.bn[0].data_ptr()
-                or bn.running_var.data_ptr() != self.bn[1].data_ptr()):
-            self.bind()
-            for g in ("A", "B"):
-                if self.opt[g] is not None:
-                    self._attach_state(g)
-
-    def invalidate(self):
-        """Parameters were modified in place from outside: supports must be recomputed."""
-        self.supports_fresh = False
+    def _params_bound(self):
+        """Every parameter still points where bind() left it."""
+        return [prm.data_ptr() for prm, _ in self.pairs] == self.bound_ptrs
 
     # ------------------------------------------------------------------ optimizers
     def _group_params(self, g):
-        n_emb = 1 + self.n + 6
-        pr = [prm for prm, _ in self.pairs]
-        return pr[:n_emb] if g == "A" else pr[n_emb:]
+        return self.group_params[g]
 
     def _attach_state(self, g):
         st = self.opt[g]
@@ -240,6 +202,13 @@ class FitEngine:
         self._attach_state(g)
         return st
 
+    def _bind_stepped(self, flags, oA, oB):
+        """Bind the optimizers that an update with these flags steps."""
+        if flags & nat.STEP_A:
+            self.bind_optimizer("A", oA)
+        if flags & nat.STEP_B:
+            self.bind_optimizer("B", oB)
+
     def _new_moments(self, g):
         """Zeroed Adam moment buffers of group g: rows of the replica pack when packed."""
         if self.pack is not None:
@@ -249,6 +218,244 @@ class FitEngine:
             return m, v
         base = self.emb if g == "A" else self.fac
         return torch.zeros_like(base), torch.zeros_like(base)
+
+    def _sync_steps(self):
+        for g in ("A", "B"):
+            st = self.opt[g]
+            if st is not None:
+                st["step"].fill_(float(st["t"]))
+
+    def _count_steps(self, flags, nsteps):
+        """The groups that flags step have taken nsteps more Adam steps."""
+        if flags & nat.STEP_A:
+            self.opt["A"]["t"] += nsteps
+        if flags & nat.STEP_B:
+            self.opt["B"]["t"] += nsteps
+        self._sync_steps()
+
+    # ------------------------------------------------------------------ hyper-parameters
+    def _bn_hyper(self):
+        """(eps, momentum) of the embedder's BatchNorm; None when it has none."""
+        return None
+
+    def _hyper(self):
+        m = self.model
+        gA = self.opt["A"]["opt"].param_groups[0] if self.opt["A"] else None
+        gB = self.opt["B"]["opt"].param_groups[0] if self.opt["B"] else None
+
+        def adam(gr):
+            if gr is None:
+                return (0.0, (0.9, 0.999), 1e-8, 0.0)
+            return (float(gr["lr"]), tuple(float(b) for b in gr["betas"]), float(gr["eps"]), float(gr["weight_decay"]))
+
+        bn = self._bn_hyper()
+        key = (m.FORECAST_COEFF, m.FACTOR_SCORE_COEFF, m.FACTOR_COS_SIM_COEFF, m.FACTOR_WEIGHT_L1_COEFF,
+               getattr(m, "FACTOR_WEIGHT_SMOOTHING_PENALTY_COEFF", 0.0), m.ADJ_L1_REG_COEFF, adam(gA), adam(gB), bn)
+        if key != self.hyper_key:
+            h = nat.ReplicaHyper()
+            (h.c_forecast, h.c_factor, h.c_cos, h.c_fwl1, h.c_smooth, h.c_adj) = [float(x) for x in key[:6]]
+            h.bn_eps, h.bn_momentum = bn or (1e-5, 0.1)  # without BatchNorm: unused
+            h.A = nat.adam_hyper(*key[6])
+            h.B = nat.adam_hyper(*key[7])
+            raw = np.frombuffer(bytes(h), dtype=np.uint8).copy()
+            self.hyper_dev = torch.from_numpy(raw).to(self.device)
+            self.hyper_key = key
+        return self.hyper_dev
+
+    # ------------------------------------------------------------------ workspace
+    def check_device_status(self, where="check"):
+        """Raise if the kernel chain logged a failure in its workspace since the last check
+        (FitEngine's merged backward does); a chain without a status word has nothing to read."""
+
+    def _before_growth(self):
+        """workspace() is about to replace the workspace."""
+
+    def _extra_workspaces(self, d):
+        """{attribute: bytes} of the workspaces this chain needs beside the shared one."""
+        return {}
+
+    def workspace(self, Bmax, T):
+        """The Dims of a launch of up to Bmax windows; the workspaces grow to hold it."""
+        Bmax = max(int(Bmax), 1)
+        if self.ws_dims is not None and self.ws_dims[0] >= Bmax:
+            return self.dims(self.ws_dims[0], T)
+        self._before_growth()
+        d = self.dims(Bmax, T)
+        sizes = {"ws": nat.lib().redcliff_workspace_bytes(ctypes.byref(d))}
+        sizes.update(self._extra_workspaces(d))
+        if 0 in sizes.values():
+            nat.check(*self.WS_ERROR)
+        self._check_layout(d)
+        for name, nbytes in sizes.items():
+            setattr(self, name, torch.zeros(nbytes // 4, device=self.device, dtype=torch.float32))
+        self.ws_dims = (Bmax,)
+        self.ws_off = nat.workspace_layout(d)
+        return d
+
+    def _check_layout(self, d):
+        """eo / fo restate rc_emb_off / rc_cemb_poff / rc_fac_off (csrc/rc_common.h) and
+        nothing else ties the two together: compare the totals with the library's when a workspace
+        is made, the engine's first call into it."""
+        got = (self._lib_emb_params(d), nat.lib().redcliff_fac_param_count(ctypes.byref(d)))
+        want = (self.eo["total"], self.fo["total"])
+        if got != want:
+            raise RuntimeError("packed parameter layout out of step with libredcliff_hip.so: (embedder, factor) "
+                               "floats %s here, %s in the library" % (want, got))
+
+    # ------------------------------------------------------------------ data
+    def _batch_stats(self, X, rows, sizes):
+        """Per-batch statistics of the batches (rows / sizes) of the device windows X that the
+        chain wants precomputed; None when it wants none."""
+        return None
+
+    def stage(self, X, Y):
+        """One host batch -> a dataset dict of that one batch (see cache_dataset) on the device,
+        with the Dims of its launch under "d"."""
+        X = X.to(self.device, torch.float32).contiguous()
+        B, T, p = X.shape
+        if p != self.p:
+            raise ValueError("expected %d channels, got %d" % (self.p, p))
+        lab = select_labels(Y.to(self.device), self.K, self.Lmax) if Y is not None else None
+        d = self.workspace(B, T)
+        return {"X": X, "lab": lab, "rows": _ROW0, "sizes": np.asarray([B], dtype=np.int32),
+                "stats": self._batch_stats(X, _ROW0, [B]),
+                "T": T, "Bmax": B, "len": 1, "d": d}
+
+    def cache_dataset(self, loader):
+        """Upload an iterable of (X, Y) batches once; later epochs replay the same order
+        (the reference DataLoader has no shuffling: data/synthetic_datasets.py:272-276)."""
+        key = id(loader)
+        if key in self.dataset_cache:
+            return self.dataset_cache[key]
+        xs, ys, sizes = [], [], []
+        for X, Y in loader:
+            xs.append(X.to(torch.float32))
+            ys.append(select_labels(Y, self.K, self.Lmax) if Y is not None else torch.zeros(X.shape[0], self.K))
+            sizes.append(int(X.shape[0]))
+        Xall = torch.cat(xs, 0).to(self.device).contiguous()
+        lab = torch.cat(ys, 0).to(self.device, torch.float32).contiguous()
+        rows = np.cumsum([0] + sizes[:-1]).astype(np.int64)
+        ds = {"X": Xall, "lab": lab, "rows": rows, "sizes": np.asarray(sizes, dtype=np.int32),
+              "stats": self._batch_stats(Xall, rows, sizes), "T": int(Xall.shape[1]), "Bmax": max(sizes),
+              "len": len(sizes), "loader": loader}
+        self.dataset_cache[key] = ds
+        return ds
+
+    def _batches(self, ds, rows, sizes, d):
+        """(rows, sizes, Dims) of a launch over `ds`: all its batches unless rows / sizes name
+        some, with the Dims given, staged with it or of the current workspace."""
+        if d is None:
+            d = ds["d"] if "d" in ds else self.workspace(ds["Bmax"], ds["T"])
+        return ds["rows"] if rows is None else rows, ds["sizes"] if sizes is None else sizes, d
+
+    # ------------------------------------------------------------------ step launch
+    def _fresh_state(self):
+        """Pick up changes made outside the kernels: an optimizer stepped by torch (its shared
+        step tensor moved)."""
+        for g in ("A", "B"):
+            st = self.opt[g]
+            if st is not None:
+                tv = int(float(st["step"]))
+                if tv != st["t"]:
+                    st["t"] = tv
+
+    def _step_args(self, d, flags, X, lab):
+        """The StepArgs fields every chain reads."""
+        self._fresh_state()
+        a = nat.StepArgs()
+        a.d = d
+        a.flags = flags
+        stA, stB = self.opt["A"], self.opt["B"]
+        a.tA = (stA["t"] + 1) if stA else 1
+        a.tB = (stB["t"] + 1) if stB else 1
+        a.X = X.data_ptr()
+        a.labels = lab.data_ptr() if lab is not None else None
+        a.emb, a.emb_stride = self.emb.data_ptr(), self.emb.numel()
+        a.fac, a.fac_stride = self.fac.data_ptr(), self.fac.numel()
+        a.emb_m, a.emb_v = (stA["m"].data_ptr(), stA["v"].data_ptr()) if stA else (self.emb.data_ptr(),) * 2
+        a.fac_m, a.fac_v = (stB["m"].data_ptr(), stB["v"].data_ptr()) if stB else (self.fac.data_ptr(),) * 2
+        a.hyper = self._hyper().data_ptr()
+        a.ws, a.ws_bytes = self.ws.data_ptr(), self.ws.numel() * 4
+        a.acc = self.acc.data_ptr()
+        a.confusion = self.conf.data_ptr()
+        return a
+
+    def gc_norms(self):
+        """(G (K,p,p,L), G0 (K,p,p)) of the current factor weights."""
+        self.ensure_bound()
+        d = nat.Dims(R=1, Bmax=1, T=self.L, p=self.p, L=self.L, K=self.K, h=self.h, F=self.L, n=1, H=1, M1=1,
+                     nsup=0, use_sigmoid=0, sigmoid_ecc=0.0)
+        G = torch.empty(self.K, self.p, self.p, self.L, device=self.device, dtype=torch.float32)
+        G0 = torch.empty(self.K, self.p, self.p, device=self.device, dtype=torch.float32)
+        nat.check(nat.lib().redcliff_gc_norms(ctypes.byref(d), ptr(self.fac), self.fac.numel(), ptr(G), ptr(G0),
+                                              _stream()), "gc_norms")
+        return G, G0
+
+
+class FitEngine(PackedEngine):
+    """The fit of a model whose factor-score embedder is the DGCNN."""
+
+    def __init__(self, model):
+        self.dgcnn = g = model.factor_score_embedder.dgcnn.dgcnn
+        self.n = g.num_layers
+        self.H = g.hid_channels
+        self.bn = torch.empty(2, g.in_channels, device=g.A.device, dtype=torch.float32)
+        self.supports_fresh = False
+        self._a_version = -1
+        super().__init__(model, g.in_channels, g.A.device)
+
+    # ------------------------------------------------------------------ layout / binding
+    def _emb_layout(self):
+        p, n, F, H, K = self.p, self.n, self.F, self.H, self.K
+        o = {"A": 0}
+        o["gcW"] = o["A"] + p * p
+        o["bnw"] = o["gcW"] + n * F * H
+        o["bnb"] = o["bnw"] + F
+        o["fc1W"] = o["bnb"] + F
+        o["fc1b"] = o["fc1W"] + M1 * p * H
+        o["fc2W"] = o["fc1b"] + M1
+        o["fc2b"] = o["fc2W"] + K * M1
+        o["total"] = o["fc2b"] + K
+        return o
+
+    def _emb_pairs(self):
+        g, o, E = self.dgcnn, self.eo, self.emb
+        p, n, F, H, K = self.p, self.n, self.F, self.H, self.K
+        pairs = [(g.A, E[o["A"]:o["A"] + p * p].view(p, p))]
+        for i in range(n):
+            pairs.append((g.layer1.gc1[i].weight, E[o["gcW"] + i * F * H:o["gcW"] + (i + 1) * F * H].view(F, H)))
+        pairs += [(g.BN1.weight, E[o["bnw"]:o["bnw"] + F]), (g.BN1.bias, E[o["bnb"]:o["bnb"] + F]),
+                  (g.fc1.linear.weight, E[o["fc1W"]:o["fc1W"] + M1 * p * H].view(M1, p * H)),
+                  (g.fc1.linear.bias, E[o["fc1b"]:o["fc1b"] + M1]),
+                  (g.fc2.linear.weight, E[o["fc2W"]:o["fc2W"] + K * M1].view(K, M1)),
+                  (g.fc2.linear.bias, E[o["fc2b"]:o["fc2b"] + K])]
+        return pairs
+
+    def _lib_emb_params(self, d):
+        return nat.lib().redcliff_emb_param_count(ctypes.byref(d))
+
+    def bind(self, copy=True):
+        super().bind(copy)
+        bnm = self.dgcnn.BN1
+        with torch.no_grad():
+            self.bn[0].copy_(bnm.running_mean)
+            self.bn[1].copy_(bnm.running_var)
+            bnm.running_mean = self.bn[0]
+            bnm.running_var = self.bn[1]
+        self.supports_fresh = False
+
+    def ensure_bound(self):
+        bn = self.dgcnn.BN1
+        if (not self._params_bound() or bn.running_mean.data_ptr() != self.bn[0].data_ptr()
+                or bn.running_var.data_ptr() != self.bn[1].data_ptr()):
+            self.bind()
+            for g in ("A", "B"):
+                if self.opt[g] is not None:
+                    self._attach_state(g)
+
+    def invalidate(self):
+        """Parameters were modified in place from outside: supports must be recomputed."""
+        self.supports_fresh = False
 
     def attach_pack(self, pack, index):
         """Move this fit's parameters, BatchNorm buffers and Adam moments into row `index`
@@ -274,37 +481,9 @@ class FitEngine:
             st["m"], st["v"] = m, v
             self._attach_state(g)
 
-    def _sync_steps(self):
-        for g in ("A", "B"):
-            st = self.opt[g]
-            if st is not None:
-                st["step"].fill_(float(st["t"]))
-
-    # ------------------------------------------------------------------ hyper-parameters
-    def _hyper(self):
-        m = self.model
+    def _bn_hyper(self):
         bnm = self.dgcnn.BN1
-        gA = self.opt["A"]["opt"].param_groups[0] if self.opt["A"] else None
-        gB = self.opt["B"]["opt"].param_groups[0] if self.opt["B"] else None
-
-        def adam(gr):
-            if gr is None:
-                return (0.0, (0.9, 0.999), 1e-8, 0.0)
-            return (float(gr["lr"]), tuple(float(b) for b in gr["betas"]), float(gr["eps"]), float(gr["weight_decay"]))
-
-        key = (m.FORECAST_COEFF, m.FACTOR_SCORE_COEFF, m.FACTOR_COS_SIM_COEFF, m.FACTOR_WEIGHT_L1_COEFF,
-               getattr(m, "FACTOR_WEIGHT_SMOOTHING_PENALTY_COEFF", 0.0), m.ADJ_L1_REG_COEFF, float(bnm.eps),
-               float(bnm.momentum if bnm.momentum is not None else 0.1), adam(gA), adam(gB))
-        if key != self.hyper_key:
-            h = nat.ReplicaHyper()
-            (h.c_forecast, h.c_factor, h.c_cos, h.c_fwl1, h.c_smooth, h.c_adj) = [float(x) for x in key[:6]]
-            h.bn_eps, h.bn_momentum = key[6], key[7]
-            h.A = nat.adam_hyper(key[8][0], key[8][1], key[8][2], key[8][3])
-            h.B = nat.adam_hyper(key[9][0], key[9][1], key[9][2], key[9][3])
-            raw = np.frombuffer(bytes(h), dtype=np.uint8).copy()
-            self.hyper_dev = torch.from_numpy(raw).to(self.device)
-            self.hyper_key = key
-        return self.hyper_dev
+        return float(bnm.eps), float(bnm.momentum if bnm.momentum is not None else 0.1)
 
     # ------------------------------------------------------------------ workspace
     def dims(self, Bmax, T):
@@ -327,21 +506,9 @@ class FitEngine:
         if self.ws is not None:
             self.raise_on_status(self.status_view().cpu().numpy(), where)
 
-    def workspace(self, Bmax, T):
-        Bmax = max(int(Bmax), 1)
-        if self.ws_dims is not None and self.ws_dims[0] >= Bmax:
-            d = self.dims(self.ws_dims[0], T)
-        else:
-            self.check_device_status("workspace growth")  # the old workspace's word would be lost
-            d = self.dims(Bmax, T)
-            nbytes = nat.lib().redcliff_workspace_bytes(ctypes.byref(d))
-            if nbytes == 0:
-                nat.check(-1, "workspace_bytes")
-            self.ws = torch.zeros(nbytes // 4, device=self.device, dtype=torch.float32)
-            self.ws_dims = (Bmax,)
-            self.ws_off = nat.workspace_layout(d)
-            self.supports_fresh = False
-        return d
+    def _before_growth(self):
+        self.check_device_status("workspace growth")  # the old workspace's word would be lost
+        self.supports_fresh = False
 
     # ------------------------------------------------------------------ data
     def bn_stats(self, d, X, N, B):
@@ -351,87 +518,31 @@ class FitEngine:
                                                     _stream()), "bn_batch_stats")
         return st
 
-    def stage(self, X, Y):
-        """One host batch -> device tensors (X (B,T,p), labels (B,K), BN batch stats)."""
-        X = X.to(self.device, torch.float32).contiguous()
-        B, T, p = X.shape
-        if p != self.p:
-            raise ValueError("expected %d channels, got %d" % (self.p, p))
-        lab = select_labels(Y.to(self.device), self.K, self.Lmax) if Y is not None else None
-        d = self.workspace(B, T)
-        st = self.bn_stats(d, X, B, B)
-        return X, lab, st, d
-
-    def cache_dataset(self, loader):
-        """Upload an iterable of (X, Y) batches once; later epochs replay the same order
-        (the reference DataLoader has no shuffling: data/synthetic_datasets.py:272-276)."""
-        key = id(loader)
-        if key in self.dataset_cache:
-            return self.dataset_cache[key]
-        xs, ys, sizes = [], [], []
-        for X, Y in loader:
-            xs.append(X.to(torch.float32))
-            ys.append(select_labels(Y, self.K, self.Lmax) if Y is not None else torch.zeros(X.shape[0], self.K))
-            sizes.append(int(X.shape[0]))
-        Xall = torch.cat(xs, 0).to(self.device).contiguous()
-        lab = torch.cat(ys, 0).to(self.device, torch.float32).contiguous()
-        rows = np.cumsum([0] + sizes[:-1]).astype(np.int64)
+    def _batch_stats(self, X, rows, sizes):
+        """BatchNorm batch statistics [nbatch][2][F] of every batch."""
         # the BatchNorm statistics kernel takes any batch size; the step workspace is sized for
         # the batches (a data-parallel fit's global batches may exceed one launch's Bmax: it
         # sizes the workspace for its shards itself)
-        d = self.workspace(max(sizes), Xall.shape[1]) if max(sizes) <= BMAX_LIMIT else self.dims(1, Xall.shape[1])
+        d = self.workspace(max(sizes), X.shape[1]) if max(sizes) <= BMAX_LIMIT else self.dims(1, X.shape[1])
         if all(s == sizes[0] for s in sizes[:-1]) and sizes[-1] <= sizes[0]:
             # consecutive equal batches (a ragged last one allowed): one launch for all of them
-            stats = self.bn_stats(d, Xall, int(Xall.shape[0]), sizes[0])
-        else:
-            stats = torch.cat([self.bn_stats(d, Xall[r:r + s], s, s) for r, s in zip(rows, sizes)], 0)
-        ds = {"X": Xall, "lab": lab, "rows": rows, "sizes": np.asarray(sizes, dtype=np.int32),
-              "stats": stats.contiguous(), "T": int(Xall.shape[1]), "Bmax": max(sizes),
-              "len": len(sizes), "loader": loader}
-        self.dataset_cache[key] = ds
-        return ds
+            return self.bn_stats(d, X, int(X.shape[0]), sizes[0])
+        return torch.cat([self.bn_stats(d, X[r:r + s], s, s) for r, s in zip(rows, sizes)], 0).contiguous()
 
     # ------------------------------------------------------------------ step launch
     def _fresh_state(self):
-        """Pick up changes made outside the kernels: an optimizer stepped by torch (its shared
-        step tensor moved) and an adjacency A modified by a torch op (A's version counter, shared
-        with the packed buffer it views, moved) -- the supports must then be rebuilt."""
-        for g in ("A", "B"):
-            st = self.opt[g]
-            if st is not None:
-                tv = int(float(st["step"]))
-                if tv != st["t"]:
-                    st["t"] = tv
+        """Also an adjacency A modified by a torch op (A's version counter, shared with the
+        packed buffer it views, moved) -- the supports must then be rebuilt."""
+        super()._fresh_state()
         if self.supports_fresh and self.dgcnn.A._version != self._a_version:
             self.supports_fresh = False
 
     def _args(self, d, flags, nbn, X, lab, stats):
-        self._fresh_state()
-        a = nat.StepArgs()
-        a.d = d
-        a.flags = flags | (0 if self.supports_fresh else nat.REFRESH_SUPPORTS)
+        a = self._step_args(d, flags, X, lab)
+        a.flags |= 0 if self.supports_fresh else nat.REFRESH_SUPPORTS
         a.n_bn_updates = nbn
-        stA, stB = self.opt["A"], self.opt["B"]
-        a.tA = (stA["t"] + 1) if stA else 1
-        a.tB = (stB["t"] + 1) if stB else 1
-        a.X = X.data_ptr()
-        a.labels = lab.data_ptr() if lab is not None else None
         a.bn_stats = stats.data_ptr() if stats is not None else None
-        a.emb, a.emb_stride = self.emb.data_ptr(), self.emb.numel()
-        a.fac, a.fac_stride = self.fac.data_ptr(), self.fac.numel()
-        if stA:
-            a.emb_m, a.emb_v = stA["m"].data_ptr(), stA["v"].data_ptr()
-        else:
-            a.emb_m = a.emb_v = self.emb.data_ptr()
-        if stB:
-            a.fac_m, a.fac_v = stB["m"].data_ptr(), stB["v"].data_ptr()
-        else:
-            a.fac_m = a.fac_v = self.fac.data_ptr()
         a.bn_rm, a.bn_rv = self.bn[0].data_ptr(), self.bn[1].data_ptr()
-        a.hyper = self._hyper().data_ptr()
-        a.ws, a.ws_bytes = self.ws.data_ptr(), self.ws.numel() * 4
-        a.acc = self.acc.data_ptr()
-        a.confusion = self.conf.data_ptr()
         return a
 
     def _mark_fresh(self):
@@ -440,36 +551,24 @@ class FitEngine:
 
     def _after(self, flags, nbn, nsteps, bn=True):
         self._mark_fresh()
-        if flags & nat.STEP_A:
-            self.opt["A"]["t"] += nsteps
-        if flags & nat.STEP_B:
-            self.opt["B"]["t"] += nsteps
         if nbn and bn:  # (a ReplicaPack advances its replicas' counters in one add)
             self.dgcnn.BN1.num_batches_tracked.add_(nbn * nsteps)
-        self._sync_steps()
+        self._count_steps(flags, nsteps)
 
-    def run_steps(self, kinds, X, lab, stats, d, rows, sizes, oA, oB):
-        """Run the update kinds of one phase over consecutive batches (rows/sizes)."""
+    def run_steps(self, kinds, ds, oA, oB, rows=None, sizes=None, stats=None, d=None):
+        """Run the update kinds of one phase over consecutive batches of the dataset dict `ds`
+        (stage / cache_dataset): all of them, or those at rows / sizes, with `stats` the
+        statistics rows from the first of them on."""
         self.ensure_bound()
+        rows, sizes, d = self._batches(ds, rows, sizes, d)
+        stats = ds["stats"] if stats is None else stats
         for kind in kinds:
             flags, nbn = step_flags(self.model, kind, self.nsup)
             if flags == 0:
                 continue
-            if flags & nat.STEP_A:
-                self.bind_optimizer("A", oA)
-            if flags & nat.STEP_B:
-                self.bind_optimizer("B", oB)
-            if not (flags & nat.BN_TRAIN):
-                stats_p = None
-            else:
-                stats_p = stats
-            a = self._args(d, flags, nbn, X, lab, stats_p)
-            rows_a = np.ascontiguousarray(rows, dtype=np.int64)
-            sizes_a = np.ascontiguousarray(sizes, dtype=np.int32)
-            nat.check(nat.lib().redcliff_train_steps(ctypes.byref(a), len(rows_a), rows_a.ctypes.data_as(ctypes.c_void_p),
-                                                     sizes_a.ctypes.data_as(ctypes.c_void_p), 2 * self.F, _stream()),
-                      "train_steps")
-            self._after(flags, nbn, len(rows_a))
+            self._bind_stepped(flags, oA, oB)
+            a = self._args(d, flags, nbn, ds["X"], ds["lab"], stats if flags & nat.BN_TRAIN else None)
+            self._after(flags, nbn, nat.train_steps(a, rows, sizes, _stream(), "train_steps", 2 * self.F))
 
     def plan_steps(self, kind, X, lab, stats, d, rows, sizes, oA, oB):
         """A prepared epoch of one update kind: the argument block, batch order and statistics
@@ -479,15 +578,15 @@ class FitEngine:
 
     VAL_GROUP = 7  # validation batches per replicated launch (R < 8 keeps the single fit's kernel paths)
 
-    def run_values(self, X, lab, d, rows, sizes, train_bn=False, stats=None, confusion=True, grouped=True, host=True):
-        """validate_training body over consecutive batches; returns (acc[8], confusion).
+    def run_values(self, ds, d=None, train_bn=False, confusion=True, grouped=True, host=True):
+        """validate_training body over the batches of the dataset dict `ds`; returns (acc[8], confusion).
         grouped=False: one launch chain per batch (the reference's loop, used by the tests).
         host=False (eval mode): the per-batch device rows (acc [nb][8], confusion [nb][ns*ns]),
         still on the device -- finish with values_from_rows after copying them back."""
         self.ensure_bound()
         flags = nat.VALUES | (nat.CONFUSION if (confusion and self.nsup > 0) else 0)
-        rows = np.asarray(rows, dtype=np.int64)
-        sizes = np.asarray(sizes, dtype=np.int32)
+        rows, sizes, d = self._batches(ds, None, None, d)
+        X, lab = ds["X"], ds["lab"]
         if not host:
             assert not train_bn
             return self._run_values_grouped(X, lab, d, rows, sizes, flags, host=False)
@@ -497,12 +596,8 @@ class FitEngine:
         self.conf.zero_()
         if train_bn:
             flags |= nat.BN_TRAIN
-        a = self._args(d, flags, 0, X, lab, stats if train_bn else None)
-        rows_a = np.ascontiguousarray(rows, dtype=np.int64)
-        sizes_a = np.ascontiguousarray(sizes, dtype=np.int32)
-        nat.check(nat.lib().redcliff_train_steps(ctypes.byref(a), len(rows_a), rows_a.ctypes.data_as(ctypes.c_void_p),
-                                                 sizes_a.ctypes.data_as(ctypes.c_void_p), 2 * self.F, _stream()),
-                  "validate")
+        a = self._args(d, flags, 0, X, lab, ds["stats"] if train_bn else None)
+        nat.train_steps(a, rows, sizes, _stream(), "validate", 2 * self.F)
         self._mark_fresh()
         return self.acc.cpu().numpy(), self.conf.cpu().numpy().reshape(max(self.nsup, 1), max(self.nsup, 1))
 
@@ -603,17 +698,6 @@ class FitEngine:
         o = self.ws_off
         return self.ws[o["w"]:o["w"] + B * self.K].view(B, self.K).clone()
 
-    def gc_norms(self):
-        """(G (K,p,p,L), G0 (K,p,p)) of the current factor weights."""
-        self.ensure_bound()
-        d = nat.Dims(R=1, Bmax=1, T=self.L, p=self.p, L=self.L, K=self.K, h=self.h, F=self.L, n=1, H=1, M1=1,
-                     nsup=0, use_sigmoid=0, sigmoid_ecc=0.0)
-        G = torch.empty(self.K, self.p, self.p, self.L, device=self.device, dtype=torch.float32)
-        G0 = torch.empty(self.K, self.p, self.p, device=self.device, dtype=torch.float32)
-        nat.check(nat.lib().redcliff_gc_norms(ctypes.byref(d), ptr(self.fac), self.fac.numel(), ptr(G), ptr(G0),
-                                              _stream()), "gc_norms")
-        return G, G0
-
 
 class StepPlan:
     """One update kind over a fixed batch sequence (an epoch of fit(), or a bench run), with
@@ -624,10 +708,7 @@ class StepPlan:
         eng.ensure_bound()
         self.eng = eng
         self.flags, self.nbn = step_flags(eng.model, kind, eng.nsup)
-        if self.flags & nat.STEP_A:
-            eng.bind_optimizer("A", oA)
-        if self.flags & nat.STEP_B:
-            eng.bind_optimizer("B", oB)
+        eng._bind_stepped(self.flags, oA, oB)
         self.stats = stats.contiguous() if (stats is not None and self.flags & nat.BN_TRAIN) else None
         self.X, self.lab = X, lab  # keep the buffers alive
         self.a = eng._args(d, self.flags, self.nbn, X, lab, self.stats)

@@ -554,7 +554,7 @@ def _train_epoch(model, eng, train, d_train, plans, oA, oB, ep):
     else:  # several updates per batch: batch-major order as in batch_update
         for bi, (r, s) in enumerate(zip(train["rows"], train["sizes"])):
             for kind in kinds:
-                eng.run_steps([kind], train["X"], train["lab"], train["stats"][bi:bi + 1], d_train, [r], [s], oA, oB)
+                eng.run_steps([kind], train, oA, oB, [r], [s], train["stats"][bi:bi + 1], d_train)
 
 
 class _SavedState:
@@ -650,7 +650,7 @@ def _device_epochs(model, eng, tr, train, val, d_train, plans, oA, oB, iter_star
             if GC is not None and nsup > 0 and est_t.shape[0] > 0:
                 vals_d = M.gc_progress_values(GC, est_t, deltaConEps, in_degree_coeff, out_degree_coeff, host=False)
             l1_d, dots_d = M.gc_track_values(est_t, nolag_t, host=False)
-            acc_d, confv_d = eng.run_values(val["X"], val["lab"], d_train, val["rows"], val["sizes"], host=False)
+            acc_d, confv_d = eng.run_values(val, d_train, host=False)
             pending = M.fetch_async([conf_d, l1_d, dots_d, acc_d, confv_d, eng.status_view()] +
                                     ([vals_d] if vals_d is not None else []))
         spec = (it + 1 < max_iter and not (save_dir is not None and it % check_every == 0) and not freeze

@@ -178,14 +178,25 @@ class REDCLIFF_S_CMLP_withStateSmoothing(nn.Module):
         from . import cemb_engine as ce
         if ce.path_requested() != "fused" or not self.cembedder_fused_supported(Bmax):
             return None
-        W = self.factors[0].networks[0].layers[0].weight
-        if not W.is_cuda:
-            raise RuntimeError("REDCLIFF-S on MI355X: move the model to the GPU first (model.cuda()); "
-                               "there is no CPU path")
+        dev = self._gpu_of(self.factors[0].networks[0].layers[0].weight)
         eng = self.__dict__.get("_cemb_engine")
-        if eng is None or eng.device != W.device:
+        if eng is None or eng.device != dev:
             eng = self.__dict__["_cemb_engine"] = ce.CEmbEngine(self)
         return eng
+
+    def _fused_engine(self, Bmax):
+        """The engine that steps / validates batches of up to Bmax windows on a fused chain: the
+        FitEngine of a DGCNN model inside fused_supported(), the CEmbEngine of a cEmbedder model
+        (opt-in and per call, see _cemb_fused), or None: the generic path runs."""
+        return self.engine() if self.fused_supported() else self._cemb_fused(Bmax)
+
+    @staticmethod
+    def _gpu_of(t):
+        """The device of tensor t, which has to be a GPU."""
+        if not t.is_cuda:
+            raise RuntimeError("REDCLIFF-S on MI355X: move the model to the GPU first (model.cuda()); "
+                               "there is no CPU path")
+        return t.device
 
     def check_device_status(self):
         """Raise if a merged-backward hand-off wait on the device timed out since the last check
@@ -200,22 +211,16 @@ class REDCLIFF_S_CMLP_withStateSmoothing(nn.Module):
                 "gen_hidden of length 1, weights applied after simulation, embed_lag >= gen_lag, "
                 "conditional_factor_fixed_embedder); got embedder=%s num_sims=%d mode=%s gc=%s" % (
                     self.factor_score_embedder_type, self.num_sims, self.forward_pass_mode, self.primary_gc_est_mode))
-        A = self.factor_score_embedder.dgcnn.dgcnn.A
-        if not A.is_cuda:
-            raise RuntimeError("REDCLIFF-S on MI355X: move the model to the GPU first (model.cuda()); "
-                               "there is no CPU path")
+        dev = self._gpu_of(self.factor_score_embedder.dgcnn.dgcnn.A)
         nat.lib()
-        if self._engine is None or self._engine.device != A.device:
+        if self._engine is None or self._engine.device != dev:
             self._engine = FitEngine(self)
         self.factor_score_embedder.owner = weakref.ref(self)
         return self._engine
 
     def _generic(self):
         """The generic GPU path (redcliff_amd.generic) for configurations outside the fused chain."""
-        W = self.factors[0].networks[0].layers[0].weight
-        if not W.is_cuda:
-            raise RuntimeError("REDCLIFF-S on MI355X: move the model to the GPU first (model.cuda()); "
-                               "there is no CPU path")
+        self._gpu_of(self.factors[0].networks[0].layers[0].weight)
         nat.lib()
         g = self.__dict__.get("_generic_path")
         if g is None:
@@ -640,42 +645,23 @@ class REDCLIFF_S_CMLP_withStateSmoothing(nn.Module):
         if output_length != 1:
             raise NotImplementedError("output_length must be 1 (num_sims * output_length target steps)")
         kinds = phase_of_epoch(self, epoch_num)
-        ceng = None if self.fused_supported() else self._cemb_fused(X.shape[0])
-        if ceng is not None:  # the fused cEmbedder chain (REDCLIFF_CEMB_PATH=fused)
-            Xd, lab, d = ceng.stage(X, Y)
-            if running_factor_score_confusion_matrix is not None:
-                ceng.conf.zero_()
-            ceng.run_steps(kinds, Xd, lab, d, [0], [Xd.shape[0]], optimizerA, optimizerB)
-            gp = self.__dict__.get("_generic_path")
-            if gp is not None:  # the engine's moments and step counts are the optimizers' state now
-                for g, opt in (("A", optimizerA), ("B", optimizerB)):
-                    if ceng.opt[g] is not None and ceng.opt[g]["opt"] is opt:
-                        gp._adams.pop(id(opt), None)
-            self._set_module_modes(kinds[-1] if kinds else None)
-            if running_factor_score_confusion_matrix is not None and self.num_supervised_factors > 0:
-                n = self.num_supervised_factors
-                running_factor_score_confusion_matrix += ceng.conf.cpu().numpy().reshape(n, n)
-            return best_model, running_factor_score_confusion_matrix
-        if not self.fused_supported():
+        conf_in = running_factor_score_confusion_matrix
+        n = self.num_supervised_factors
+        eng = self._fused_engine(X.shape[0])
+        if eng is None:
             dev = self._device()
-            n = self.num_supervised_factors
-            conf = np.zeros((n, n)) if (running_factor_score_confusion_matrix is not None and n > 0) else None
+            conf = np.zeros((n, n)) if (conf_in is not None and n > 0) else None
             self._generic().batch_update(kinds, X.to(dev, torch.float32), Y.to(dev, torch.float32), optimizerA,
                                          optimizerB, output_length, conf)
-            self._set_module_modes(kinds[-1] if kinds else None)
-            if conf is not None:
-                running_factor_score_confusion_matrix += conf
-            return best_model, running_factor_score_confusion_matrix
-        eng = self.engine()
-        Xd, lab, st, d = eng.stage(X, Y)
-        if running_factor_score_confusion_matrix is not None:
-            eng.conf.zero_()
-        eng.run_steps(kinds, Xd, lab, st, d, [0], [Xd.shape[0]], optimizerA, optimizerB)
+        else:
+            if conf_in is not None:
+                eng.conf.zero_()
+            eng.run_steps(kinds, eng.stage(X, Y), optimizerA, optimizerB)
+            conf = eng.conf.cpu().numpy().reshape(n, n) if (conf_in is not None and n > 0) else None
         self._set_module_modes(kinds[-1] if kinds else None)
-        if running_factor_score_confusion_matrix is not None and self.num_supervised_factors > 0:
-            n = self.num_supervised_factors
-            running_factor_score_confusion_matrix += eng.conf.cpu().numpy().reshape(n, n)
-        return best_model, running_factor_score_confusion_matrix
+        if conf is not None:
+            conf_in += conf
+        return best_model, conf_in
 
     def _set_module_modes(self, kind):
         if kind in ("pretrain_embedder", "combined"):
@@ -690,42 +676,29 @@ class REDCLIFF_S_CMLP_withStateSmoothing(nn.Module):
                           factor_score_val_tpr_history=None, factor_score_val_tnr_history=None,
                           factor_score_val_fpr_history=None, factor_score_val_fnr_history=None):
         """...withStateSmoothing.py:1650-1790: coefficient-normalised loss terms averaged over batches."""
-        ceng = None
+        hists = (factor_score_val_acc_history, factor_score_val_tpr_history, factor_score_val_tnr_history,
+                 factor_score_val_fpr_history, factor_score_val_fnr_history)
+        Bmax = 0  # of the batches a cEmbedder chain would run (it covers output_length == 1)
         if not self.fused_supported() and output_length == 1:
-            sizes = [int(Xb.shape[0]) for Xb, _ in X_val]
-            ceng = self._cemb_fused(max(sizes)) if sizes else None
-        if ceng is not None:  # the fused cEmbedder chain (REDCLIFF_CEMB_PATH=fused)
-            self.factor_score_embedder.eval()
-            for f in self.factors:
-                f.eval()
-            ds = ceng.cache_dataset(X_val)
-            d = ceng.workspace(ds["Bmax"], ds["T"])
-            acc, conf = ceng.run_values(ds["X"], ds["lab"], d, ds["rows"], ds["sizes"])
-            return self._validation_tuple(acc, float(ds["len"]), conf, factor_score_val_acc_history,
-                                          factor_score_val_tpr_history, factor_score_val_tnr_history,
-                                          factor_score_val_fpr_history, factor_score_val_fnr_history)
-        if not self.fused_supported():
+            Bmax = max([int(Xb.shape[0]) for Xb, _ in X_val], default=0)
+        eng = self._fused_engine(Bmax) if (Bmax > 0 or self.fused_supported()) else None
+        if eng is None:
             for f in self.factors:
                 f.eval()
             avg, conf = self._generic().validate(X_val, output_length)
             acc = [avg[k] for k in ("forecast", "factor", "cos", "fw_l1", "smooth", "adj", "combo")] + [1.0]
-            return self._validation_tuple(acc, 1.0, conf, factor_score_val_acc_history,
-                                          factor_score_val_tpr_history, factor_score_val_tnr_history,
-                                          factor_score_val_fpr_history, factor_score_val_fnr_history)
+            return self._validation_tuple(acc, 1.0, conf, *hists)
         self.factor_score_embedder.eval()
         for f in self.factors:
             f.eval()
-        return self._validate_fused(X_val, False, factor_score_val_acc_history, factor_score_val_tpr_history,
-                                    factor_score_val_tnr_history, factor_score_val_fpr_history,
-                                    factor_score_val_fnr_history)
+        return self._validate_fused(X_val, False, *hists, eng=eng)
 
-    def _validate_fused(self, X_val, fresh_histories, *hists):
-        """validate_training on the fused engine without touching the module flags (fit() sets
-        them once); fresh_histories: five new confusion-history lists (fit's call)."""
-        eng = self.engine()
+    def _validate_fused(self, X_val, fresh_histories, *hists, eng=None):
+        """validate_training on a fused engine (default: engine()) without touching the module flags
+        (fit() sets them once); fresh_histories: five new confusion-history lists (fit's call)."""
+        eng = eng or self.engine()
         ds = eng.cache_dataset(X_val)
-        d = eng.workspace(ds["Bmax"], ds["T"])
-        acc, conf = eng.run_values(ds["X"], ds["lab"], d, ds["rows"], ds["sizes"])
+        acc, conf = eng.run_values(ds)
         eng.check_device_status("validate_training")
         if fresh_histories:
             hists = [[] for _ in range(5)]

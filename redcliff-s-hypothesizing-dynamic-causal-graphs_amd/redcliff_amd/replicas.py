@@ -371,17 +371,12 @@ class ReplicaPack:
         for kind in kinds:
             flags, nbn = flags_for(kind, self.engines[0].nsup)
             a, engs = self._args(d, flags, nbn, ds, stats if flags & nat.BN_TRAIN else None, active)
-            rows_a = np.ascontiguousarray(rows, dtype=np.int64)
-            sizes_a = np.ascontiguousarray(sizes, dtype=np.int32)
-            nat.check(nat.lib().redcliff_train_steps(ctypes.byref(a), len(rows_a),
-                                                     rows_a.ctypes.data_as(ctypes.c_void_p),
-                                                     sizes_a.ctypes.data_as(ctypes.c_void_p), 2 * self.engines[0].F,
-                                                     _stream()), "packed train_steps")
+            n = nat.train_steps(a, rows, sizes, _stream(), "packed train_steps", 2 * self.engines[0].F)
             for e in engs:
-                e._after(flags, nbn, len(rows_a), bn=False)
+                e._after(flags, nbn, n, bn=False)
             if nbn:
                 with torch.no_grad():
-                    self.nbt.add_(self._mask(active), alpha=nbn * len(rows_a))
+                    self.nbt.add_(self._mask(active), alpha=nbn * n)
             for e in self.engines:
                 e.supports_fresh = False  # the single-fit workspace's supports are stale now
 
@@ -423,11 +418,7 @@ class ReplicaPack:
         d = self._workspace(max(int(ds["Bmax"]), 1), ds["T"])
         flags = nat.VALUES | (nat.CONFUSION if e0.nsup > 0 else 0)
         a, _ = self._args(d, flags, 0, ds, None, active)
-        rows_a = np.ascontiguousarray(ds["rows"], dtype=np.int64)
-        sizes_a = np.ascontiguousarray(ds["sizes"], dtype=np.int32)
-        nat.check(nat.lib().redcliff_train_steps(ctypes.byref(a), len(rows_a), rows_a.ctypes.data_as(ctypes.c_void_p),
-                                                 sizes_a.ctypes.data_as(ctypes.c_void_p), 2 * e0.F, _stream()),
-                  "packed validate")
+        nat.train_steps(a, ds["rows"], ds["sizes"], _stream(), "packed validate", 2 * e0.F)
         ns = max(e0.nsup, 1)
         if not host:
             return self.acc, self.conf

@@ -122,10 +122,10 @@ def main():
             print(path, phase, res["phases"][phase][path]["median_ms"], flush=True)
         if path == "fused":  # one C call per `steps` steps (an epoch of fit())
             eng = m._cemb_fused(B)
-            Xd, lab, d = eng.stage(X, Y)
+            staged = eng.stage(X, Y)
             for phase, kind in (("acclimation", "acclimate"), ("combined", "combined")):
                 def runc(n, kind=kind):
-                    eng.run_steps([kind], Xd, lab, d, [0] * n, [B] * n, oA, oB)
+                    eng.run_steps([kind], staged, oA, oB, [0] * n, [B] * n)
                 res["phases"][phase]["fused_one_call"] = measure(runc, args.steps, args.warmup, args.reps)
     # the DGCNN C1(K=4) step, for context
     c1 = bench.CONFIGS["c1k4"]
@@ -135,15 +135,16 @@ def main():
     Xc, Yc = Xc.cuda(), Yc.cuda()
     md.batch_update(0, 0, Xc, Yc, dA, dB, 1)
     deng = md.engine()
-    Xs, labs, st, dd = deng.stage(Xc, Yc)
-    stn = dict((n, st.repeat(n, 1, 1).contiguous()) for n in (args.steps, args.warmup))  # one statistics row per step
+    dstaged = deng.stage(Xc, Yc)
+    # one statistics row per step
+    stn = dict((n, dstaged["stats"].repeat(n, 1, 1).contiguous()) for n in (args.steps, args.warmup))
     for phase, epoch, kind in (("acclimation", 1, "acclimate"), ("combined", 2, "combined")):
         def rund(n, epoch=epoch):
             for _ in range(n):
                 md.batch_update(epoch, 0, Xc, Yc, dA, dB, 1)
 
         def rundc(n, kind=kind):
-            deng.run_steps([kind], Xs, labs, stn[n], dd, [0] * n, [c1["B"]] * n, dA, dB)
+            deng.run_steps([kind], dstaged, dA, dB, [0] * n, [c1["B"]] * n, stn[n])
         ph = res["phases"][phase]
         ph["dgcnn_c1k4"] = measure(rund, args.steps, args.warmup, args.reps)
         ph["dgcnn_c1k4_one_call"] = measure(rundc, args.steps, args.warmup, args.reps)

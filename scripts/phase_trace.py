@@ -38,10 +38,9 @@ def main():
     loader = [(X[i:i + c["B"]], Y[i:i + c["B"]]) for i in range(0, X.shape[0], c["B"])]
     eng = model.engine()
     ds = eng.cache_dataset(loader)
-    d = eng.workspace(ds["Bmax"], ds["T"])
     idx = np.arange(args.steps) % len(loader)
     stats = ds["stats"][torch.as_tensor(idx, device=dev)].contiguous()
-    eng.run_steps(["combined"], ds["X"], ds["lab"], stats, d, ds["rows"][idx], ds["sizes"][idx], oA, oB)
+    eng.run_steps(["combined"], ds, oA, oB, ds["rows"][idx], ds["sizes"][idx], stats)
     torch.cuda.synchronize()
     tot = eng.ws_off["total"]
     tr = eng.ws[tot - 32768:tot].cpu().numpy().view(np.uint64).astype(np.int64).reshape(8, 2048)

@@ -350,7 +350,8 @@ def test_two_replicas_equal_two_single_calls(fused):
         eng.bind_optimizer("B", opts[1])
         engs.append((m, opts, eng))
     e0 = engs[0][2]
-    Xd, lab, d = e0.stage(X, Y)
+    staged = e0.stage(X, Y)
+    Xd, lab, d = staged["X"], staged["lab"], staged["d"]
     flags = nat.LOSS_FORECAST | nat.LOSS_FACTOR | nat.LOSS_FWL1 | nat.LOSS_ADJ | nat.STEP_A | nat.STEP_B | nat.CONFUSION
     # packed copies of both fits (parameters, zero moments), stepped by one R = 2 call
     emb = torch.stack([e.emb for _, _, e in engs]).contiguous()
@@ -379,8 +380,7 @@ def test_two_replicas_equal_two_single_calls(fused):
     torch.cuda.synchronize()
     for r, (m, opts, eng) in enumerate(engs):  # the same step as an R = 1 call of each fit
         eng.conf.zero_()
-        Xr, labr, dr = eng.stage(X, Y)
-        eng.run_steps(["combined"], Xr, labr, dr, [0], [B], opts[0], opts[1])
+        eng.run_steps(["combined"], eng.stage(X, Y), opts[0], opts[1], [0], [B])
         torch.cuda.synchronize()
         np.testing.assert_array_equal(emb[r].cpu().numpy(), eng.emb.cpu().numpy(), err_msg="replica %d embedder" % r)
         np.testing.assert_array_equal(fac[r].cpu().numpy(), eng.fac.cpu().numpy(), err_msg="replica %d factors" % r)

@@ -247,8 +247,8 @@ def test_grouped_validation_bitwise_equals_batch_loop(path, monkeypatch):
     eng = m.engine()
     ds = eng.cache_dataset(val)
     d = eng.workspace(ds["Bmax"], ds["T"])
-    acc_g, conf_g = eng.run_values(ds["X"], ds["lab"], d, ds["rows"], ds["sizes"])
-    acc_s, conf_s = eng.run_values(ds["X"], ds["lab"], d, ds["rows"], ds["sizes"], grouped=False)
+    acc_g, conf_g = eng.run_values(ds, d)
+    acc_s, conf_s = eng.run_values(ds, d, grouped=False)
     assert acc_s[7] == len(val)
     np.testing.assert_array_equal(acc_g, acc_s)
     np.testing.assert_array_equal(conf_g, conf_s)
