@@ -371,11 +371,47 @@ typedef struct RedcliffScoreArgs {
 size_t redcliff_score_recording_workspace_bytes(const RedcliffDims* d);
 int redcliff_score_recording(const RedcliffScoreArgs* a, void* stream);
 
+/* ---- scoring whole recordings of cEmbedder models (general_utils/misc.py:57-81 on the embedder of
+ * models/redcliff_factor_score_embedders.py:183-273) ----
+ * Purely additive entries: REDCLIFF_ABI_VERSION stays 10.
+ *
+ * The cEmbedder (K networks Conv1d(p, eh, F) -> ReLU -> 1x1 Conv1d, hidden == [eh], no wavelets) over
+ * the same sliding windows, with the same outputs w / logits / graphs, the same activations and the
+ * same argument rules and return codes as redcliff_score_recording.  The window is read time-major at
+ * every p (the cEmbedder has no p == F special case) and there is no BatchNorm:
+ *   z[u]   = be0[k][u] + sum_q We0[k][u][q] X[t0 + f][c]      (q = c*F + f ascending)
+ *   raw[k] = be1[k] + sum_u We1[k][u] relu(z[u])
+ * emb is the packed cEmbedder block (layout above: We0 | be0 | We1 | be1); the call reads it only and
+ * needs no workspace.  Of RedcliffDims only p, K, F, nsup, use_sigmoid and sigmoid_ecc are read.
+ * Limits: p <= 64, F <= 64, K <= 16, eh <= 128 (p*(F + 63) + 4096 <= 40960 floats of LDS holds inside
+ * them); outside them REDCLIFF_ELIMIT.  count == 0 launches nothing.  Stream-ordered, no host
+ * synchronisation, no atomics: the same arguments give the same bits, and a window's results do not
+ * depend on count, stride, Nrec or on its position in the launch. */
+typedef struct RedcliffCEmbScoreArgs {
+  RedcliffDims d;
+  int32_t eh;            /* cEmbedder hidden width                                             */
+  int32_t pad_;
+  const float* emb;
+  const float* X; int64_t x_rstride;
+  int32_t Nrec, T;
+  int32_t start, count, stride;
+  int32_t use_final_activation;
+  float* w; float* logits;
+  const float* tab; const float* bias; float* graphs;  /* graphs == NULL: no graph trace        */
+  int32_t Q; int32_t pad2_;
+} RedcliffCEmbScoreArgs;
+/* Host-only limit query: 0 outside the limits (with a redcliff_last_error message), else the number
+ * of recording rows one tile can stage in LDS (a tile scores up to 64 steps, fewer when
+ * (steps - 1)*stride + F would exceed this number, down to one). */
+int redcliff_cemb_score_supported(const RedcliffDims* d, int32_t eh);
+int redcliff_cemb_score_recording(const RedcliffCEmbScoreArgs* a, void* stream);
+
 /* Per-kernel HIP-event timing for benchmarking: redcliff_kernel_timing(1) brackets every
  * kernel launched by redcliff_train_step with events on its stream; redcliff_kernel_times()
- * synchronises them and returns per-kernel totals (ids 0..10: supports, emb_fwd, fac_fwd,
- * fac_bwd, emb_bwd, emb_final, fac_mix, emb_combine, fac_lead, and redcliff_score_recording's
- * score, score_graphs).  Returns the number of kernel ids.
+ * synchronises them and returns per-kernel totals (ids 0..11: supports, emb_fwd, fac_fwd,
+ * fac_bwd, emb_bwd, emb_final, fac_mix, emb_combine, fac_lead, redcliff_score_recording's
+ * score, score_graphs, and redcliff_cemb_score_recording's score_cemb).  Returns the number of
+ * kernel ids.
  * When a single fit (R == 1) splits into two kernel chains (GEMM-shaped embedder and / or
  * matrix-core factor path), the factor chain runs on an internal second stream (one per host
  * thread and device) forked from and joined back into `stream` with events, so stream

@@ -9,7 +9,7 @@
 
 // ---- optional per-kernel HIP-event timing (bench / profiling only) -------------------------
 namespace {
-enum { KT_SUPPORTS = 0, KT_EMB_FWD, KT_FAC_FWD, KT_FAC_BWD, KT_EMB_BWD, KT_EMB_FINAL, KT_FAC_MIX, KT_EMB_COMB, KT_FAC_LEAD, KT_SCORE, KT_SCORE_GRAPHS, KT_N };
+enum { KT_SUPPORTS = 0, KT_EMB_FWD, KT_FAC_FWD, KT_FAC_BWD, KT_EMB_BWD, KT_EMB_FINAL, KT_FAC_MIX, KT_EMB_COMB, KT_FAC_LEAD, KT_SCORE, KT_SCORE_GRAPHS, KT_SCORE_CEMB, KT_N };
 struct TimedLaunch {
   int id;
   hipEvent_t a, b;
@@ -719,10 +719,65 @@ int redcliff_score_recording(const RedcliffScoreArgs* a, void* stream) {
   return 0;
 }
 
+// ---- recording scoring of cEmbedder models (rc_score_cemb.hip) ----------------------------------
+// Only the embedder's dimensions play a part (Bmax, T, L, h, n, H, M1 are not read).
+static int cemb_score_dims(const RedcliffDims* d, int32_t eh) {
+  if (!d) { rc_set_error("null dims"); return REDCLIFF_EINVAL; }
+  if (d->p < 1 || d->K < 1 || d->F < 1 || eh < 1 || d->nsup < 0 || d->nsup > d->K) {
+    rc_set_error("invalid dims (p=%d K=%d F=%d eh=%d nsup=%d)", d->p, d->K, d->F, eh, d->nsup);
+    return REDCLIFF_EINVAL;
+  }
+  if (rc_score_cemb_rows_budget(*d, eh) <= 0) {
+    rc_set_error("dims outside kernel limits (cemb_score_recording: p<=64 F<=64 K<=16 eh<=128, LDS budget p*(F+63) + 4096 floats)");
+    return REDCLIFF_ELIMIT;
+  }
+  return 0;
+}
+
+int redcliff_cemb_score_supported(const RedcliffDims* d, int32_t eh) {
+  if (cemb_score_dims(d, eh) != 0) return 0;
+  return rc_score_cemb_rows_budget(*d, eh);
+}
+
+int redcliff_cemb_score_recording(const RedcliffCEmbScoreArgs* a, void* stream) {
+  if (!a) { rc_set_error("null score arguments"); return REDCLIFF_EINVAL; }
+  int e = cemb_score_dims(&a->d, a->eh);
+  if (e) return e;
+  const RedcliffDims& d = a->d;
+  if (!a->emb || !a->X || !a->w || (d.nsup > 0 && !a->logits) || (a->graphs && !a->tab)) {
+    rc_set_error("cemb_score_recording: null buffer in arguments");
+    return REDCLIFF_EINVAL;
+  }
+  if (a->Nrec < 1 || a->T < 1 || a->x_rstride < 0 || a->start < d.F || a->stride < 1 || a->count < 0 ||
+      (a->graphs && a->Q < 1)) {
+    rc_set_error("cemb_score_recording: bad arguments (Nrec=%d T=%d start=%d (>= F=%d) stride=%d count=%d Q=%d)", a->Nrec,
+                 a->T, a->start, d.F, a->stride, a->count, a->Q);
+    return REDCLIFF_EINVAL;
+  }
+  if (a->count > 0 && (int64_t)a->start + (int64_t)(a->count - 1) * a->stride > (int64_t)a->T) {
+    rc_set_error("cemb_score_recording: the last window ends at row %lld, past T=%d",
+                 (long long)a->start + (long long)(a->count - 1) * a->stride, a->T);
+    return REDCLIFF_EINVAL;
+  }
+  if (a->count == 0) return 0;
+  hipStream_t s = (hipStream_t)stream;
+  if ((e = timed(KT_SCORE_CEMB, s, [&] {
+         return rc_launch_score_cemb(d, a->eh, a->emb, a->X, a->x_rstride, a->Nrec, a->start, a->count, a->stride,
+                                     a->use_final_activation, a->w, a->logits, s);
+       })))
+    return e;
+  if (a->graphs &&
+      (e = timed(KT_SCORE_GRAPHS, s, [&] {
+         return rc_launch_score_graphs(a->w, a->tab, a->bias, a->graphs, d.K, a->Q, (int64_t)a->Nrec * a->count, s);
+       })))
+    return e;
+  return 0;
+}
+
 // Per-kernel timing: while enabled every launch of redcliff_train_step is bracketed by
 // HIP events on its stream.  redcliff_kernel_times() waits for the recorded events,
 // adds the elapsed milliseconds per kernel (ids: supports, emb_fwd, fac_fwd, fac_bwd,
-// emb_bwd, emb_final, fac_mix, emb_combine, fac_lead, score, score_graphs) into total_ms[]/counts[] and
+// emb_bwd, emb_final, fac_mix, emb_combine, fac_lead, score, score_graphs, score_cemb) into total_ms[]/counts[] and
 // clears the record.
 int redcliff_kernel_timing(int32_t enable) {
   g_timing = enable != 0;

@@ -770,3 +770,8 @@ int rc_launch_score_windows(const RedcliffDims& d, const EmbOff& eo, const float
                             const float* Zb, float* w, float* logits, hipStream_t s);
 int rc_launch_score_graphs(const float* w, const float* tab, const float* bias, float* out, int K, int Q, int64_t nwin,
                            hipStream_t s);
+// recording scoring of cEmbedder models (rc_score_cemb.hip): the LDS rows per channel a tile may
+// stage (0: outside the kernel's limits) and the sliding-window embedder
+int rc_score_cemb_rows_budget(const RedcliffDims& d, int eh);
+int rc_launch_score_cemb(const RedcliffDims& d, int eh, const float* emb, const float* X, int64_t xrs, int Nrec,
+                         int start, int count, int stride, int ufa, float* w, float* logits, hipStream_t s);

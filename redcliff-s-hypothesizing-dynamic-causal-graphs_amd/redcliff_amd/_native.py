@@ -41,10 +41,11 @@ EXPORTED = ("redcliff_abi_version", "redcliff_last_error", "redcliff_workspace_b
             "redcliff_gc_track_stats", "redcliff_device_status", "redcliff_build_id",
             "redcliff_cemb_param_count", "redcliff_cemb_workspace_bytes", "redcliff_cemb_workspace_regions",
             "redcliff_cemb_train_step", "redcliff_cemb_train_steps",
-            "redcliff_score_recording_workspace_bytes", "redcliff_score_recording")
+            "redcliff_score_recording_workspace_bytes", "redcliff_score_recording",
+            "redcliff_cemb_score_supported", "redcliff_cemb_score_recording")
 CEMB_WS_REGIONS = ("ha", "w1", "g", "g0", "E", "E0", "dE", "draw")
 KERNEL_IDS = ("supports", "emb_fwd", "fac_fwd", "fac_bwd", "emb_bwd", "emb_final", "fac_mix", "emb_combine", "fac_lead",
-              "score", "score_graphs")
+              "score", "score_graphs", "score_cemb")
 
 
 class Dims(ctypes.Structure):
@@ -95,6 +96,15 @@ class ScoreArgs(ctypes.Structure):
                 ("use_final_activation", ctypes.c_int32), ("w", _vp), ("logits", _vp),
                 ("tab", _vp), ("bias", _vp), ("graphs", _vp), ("Q", ctypes.c_int32), ("pad_", ctypes.c_int32),
                 ("ws", _vp), ("ws_bytes", ctypes.c_size_t)]
+
+
+class CEmbScoreArgs(ctypes.Structure):
+    """RedcliffCEmbScoreArgs (redcliff_cemb_score_recording)."""
+    _fields_ = [("d", Dims), ("eh", ctypes.c_int32), ("pad_", ctypes.c_int32), ("emb", _vp),
+                ("X", _vp), ("x_rstride", _i64), ("Nrec", ctypes.c_int32), ("T", ctypes.c_int32),
+                ("start", ctypes.c_int32), ("count", ctypes.c_int32), ("stride", ctypes.c_int32),
+                ("use_final_activation", ctypes.c_int32), ("w", _vp), ("logits", _vp),
+                ("tab", _vp), ("bias", _vp), ("graphs", _vp), ("Q", ctypes.c_int32), ("pad2_", ctypes.c_int32)]
 
 
 def adam_hyper(lr, betas, eps, weight_decay):
@@ -161,6 +171,8 @@ def lib():
                                             _vp]
     L.redcliff_score_recording_workspace_bytes.argtypes = [ctypes.POINTER(Dims)]
     L.redcliff_score_recording.argtypes = [ctypes.POINTER(ScoreArgs), _vp]
+    L.redcliff_cemb_score_supported.argtypes = [ctypes.POINTER(Dims), ctypes.c_int32]
+    L.redcliff_cemb_score_recording.argtypes = [ctypes.POINTER(CEmbScoreArgs), _vp]
     for name in EXPORTED[2:]:
         if name not in ("redcliff_workspace_bytes", "redcliff_emb_param_count", "redcliff_fac_param_count",
                         "redcliff_build_id", "redcliff_cemb_param_count", "redcliff_cemb_workspace_bytes",

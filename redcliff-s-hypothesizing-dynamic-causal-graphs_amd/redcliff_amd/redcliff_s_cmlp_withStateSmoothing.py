@@ -303,7 +303,9 @@ class REDCLIFF_S_CMLP_withStateSmoothing(nn.Module):
         sum(self.GC(mode, X=window, threshold=False, ignore_lag=ignore_lag)[0]) for
         mode = gc_est_mode or primary_gc_est_mode (conditional_factor_exclusive /
         conditional_factor_fixed_embedder).  Fused kernel (csrc/rc_score.hip) for DGCNN models inside
-        fused_supported() without wavelets; every other model runs the chunked route."""
+        fused_supported() without wavelets; with REDCLIFF_CEMB_PATH=fused the cEmbedder kernel
+        (csrc/rc_score_cemb.hip) for cEmbedder models without wavelets, with one embedder hidden layer
+        and lag == embed_lag; every other model runs the chunked route."""
         from . import scoring
         return scoring.score_recording(self, X, start, count, stride, use_final_activation, graphs, gc_est_mode,
                                        ignore_lag)
