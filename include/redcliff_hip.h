@@ -17,6 +17,8 @@
  *    hipError_t.  redcliff_last_error() returns a thread-local message.
  *  - R "replicas" (independent fits with identical shapes, e.g. grid-search points)
  *    may be packed into one call; every per-replica buffer has an explicit stride.
+ *    Training steps (redcliff_train_step), the cEmbedder chain and recording scoring
+ *    (redcliff_score_recording_pack) all carry the replica on a grid axis.
  *  - fp32 throughout (the reference calls .float() on every model,
  *    general_utils/model_utils.py:392,417).
  */
@@ -371,6 +373,47 @@ typedef struct RedcliffScoreArgs {
 size_t redcliff_score_recording_workspace_bytes(const RedcliffDims* d);
 int redcliff_score_recording(const RedcliffScoreArgs* a, void* stream);
 
+/* ---- scoring whole recordings with R same-shape models in one launch chain ----
+ * Purely additive entries: REDCLIFF_ABI_VERSION stays 10, no existing entry or layout changes.
+ *
+ * redcliff_score_recording for R models of one shape d (grid-search points, cross-validation folds):
+ * one supports launch, one table launch, one window-kernel launch on grid (tiles, Nrec, scored
+ * replicas) and, with graphs, one graph launch.  Replica r reads
+ *   emb + r*emb_stride                 its packed embedder block
+ *   bn_rm + r*bn_stride, bn_rv + ...   its running statistics [F] (a [2][R][F] buffer: stride F)
+ *   X + r*x_pstride                    its recording set [Nrec][T][p]; x_pstride == 0: all replicas score
+ *                                      the same X
+ *   tab + r*K*Q, bias + r*Q            its graph tables tab[R][K][Q] / bias[R][Q] (bias may be NULL)
+ * replicas / n_replicas: the replicas to score, a strictly increasing HOST array of indices < R as
+ * RedcliffStepArgs.replicas (NULL = all R; n_replicas == 0 launches nothing).  Outputs, contiguous,
+ * i = the i-th scored replica in ascending order:
+ *   w[i][rec][j][K]   logits[i][rec][j][nsup]   graphs[i][rec][j][Q]
+ * ws: redcliff_score_recording_pack_workspace_bytes(d, R) bytes (R times the single call's), private
+ * to the call.  A window's arithmetic and every order of sums are those of redcliff_score_recording:
+ * its bits depend on the dims and the replica's own data only -- not on R, the replica's index, the
+ * active list or whether X is shared -- so row i equals the single call on replica i's buffers bit
+ * for bit.  Limits and return codes as redcliff_score_recording, plus: R < 1, a bad active list,
+ * negative strides give REDCLIFF_EINVAL; R > 256 and Nrec > 65535 REDCLIFF_ELIMIT (the size query
+ * returns 0); a short workspace REDCLIFF_EWORKSPACE.  All checks precede any HIP call. */
+typedef struct RedcliffScorePackArgs {
+  RedcliffDims d;                        /* d.R is not read                                   */
+  int32_t R; int32_t pad0_;
+  const float* emb; int64_t emb_stride;
+  const float* bn_rm; const float* bn_rv; int64_t bn_stride;
+  double bn_eps;                         /* BatchNorm1d.eps (shared by the replicas)          */
+  const float* X; int64_t x_rstride; int64_t x_pstride;
+  int32_t Nrec, T;
+  int32_t start, count, stride;
+  int32_t use_final_activation;
+  float* w; float* logits;
+  const float* tab; const float* bias; float* graphs;  /* graphs == NULL: no graph trace        */
+  int32_t Q; int32_t n_replicas;
+  const int32_t* replicas;
+  void* ws; size_t ws_bytes;
+} RedcliffScorePackArgs;
+size_t redcliff_score_recording_pack_workspace_bytes(const RedcliffDims* d, int32_t R);
+int redcliff_score_recording_pack(const RedcliffScorePackArgs* a, void* stream);
+
 /* ---- scoring whole recordings of cEmbedder models (general_utils/misc.py:57-81 on the embedder of
  * models/redcliff_factor_score_embedders.py:183-273) ----
  * Purely additive entries: REDCLIFF_ABI_VERSION stays 10.
@@ -410,8 +453,9 @@ int redcliff_cemb_score_recording(const RedcliffCEmbScoreArgs* a, void* stream);
  * kernel launched by redcliff_train_step with events on its stream; redcliff_kernel_times()
  * synchronises them and returns per-kernel totals (ids 0..11: supports, emb_fwd, fac_fwd,
  * fac_bwd, emb_bwd, emb_final, fac_mix, emb_combine, fac_lead, redcliff_score_recording's
- * score, score_graphs, and redcliff_cemb_score_recording's score_cemb).  Returns the number of
- * kernel ids.
+ * score, score_graphs, and redcliff_cemb_score_recording's score_cemb; the launches of
+ * redcliff_score_recording_pack count under supports, score and score_graphs).  Returns the number
+ * of kernel ids.
  * When a single fit (R == 1) splits into two kernel chains (GEMM-shaped embedder and / or
  * matrix-core factor path), the factor chain runs on an internal second stream (one per host
  * thread and device) forked from and joined back into `stream` with events, so stream

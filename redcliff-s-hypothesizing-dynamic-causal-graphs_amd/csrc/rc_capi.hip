@@ -719,6 +719,102 @@ int redcliff_score_recording(const RedcliffScoreArgs* a, void* stream) {
   return 0;
 }
 
+// ---- recording scoring of R same-shape models in one launch chain ------------------------------
+size_t redcliff_score_recording_pack_workspace_bytes(const RedcliffDims* d, int32_t R) {
+  if (R < 1 || R > RC_MAX_ACTIVE) { rc_set_error("score_recording_pack: R=%d outside [1, %d]", R, RC_MAX_ACTIVE); return 0; }
+  if (score_dims(d) != 0) return 0;
+  return sizeof(float) * (size_t)score_ws(*d).total * (size_t)R;
+}
+
+int redcliff_score_recording_pack(const RedcliffScorePackArgs* a, void* stream) {
+  if (!a) { rc_set_error("null score arguments"); return REDCLIFF_EINVAL; }
+  int e = score_dims(&a->d);
+  if (e) return e;
+  const RedcliffDims& d = a->d;
+  if (a->R < 1) { rc_set_error("score_recording_pack: R=%d", a->R); return REDCLIFF_EINVAL; }
+  if (a->R > RC_MAX_ACTIVE) { rc_set_error("score_recording_pack: R=%d replicas (at most %d)", a->R, RC_MAX_ACTIVE); return REDCLIFF_ELIMIT; }
+  if (!a->emb || !a->bn_rm || !a->bn_rv || !a->X || !a->w || !a->ws || (d.nsup > 0 && !a->logits) ||
+      (a->graphs && !a->tab)) {
+    rc_set_error("score_recording_pack: null buffer in arguments");
+    return REDCLIFF_EINVAL;
+  }
+  if (a->emb_stride < 0 || a->bn_stride < 0 || a->x_pstride < 0) {
+    rc_set_error("score_recording_pack: negative replica stride (emb_stride=%lld bn_stride=%lld x_pstride=%lld)",
+                 (long long)a->emb_stride, (long long)a->bn_stride, (long long)a->x_pstride);
+    return REDCLIFF_EINVAL;
+  }
+  if (a->Nrec < 1 || a->T < 1 || a->x_rstride < 0 || a->start < d.F || a->stride < 1 || a->count < 0 ||
+      (a->graphs && a->Q < 1)) {
+    rc_set_error("score_recording_pack: bad arguments (Nrec=%d T=%d start=%d (>= F=%d) stride=%d count=%d Q=%d)", a->Nrec,
+                 a->T, a->start, d.F, a->stride, a->count, a->Q);
+    return REDCLIFF_EINVAL;
+  }
+  if (a->Nrec > 65535) { rc_set_error("score_recording_pack: grid too large (Nrec <= 65535)"); return REDCLIFF_ELIMIT; }
+  if (a->count > 0 && (int64_t)a->start + (int64_t)(a->count - 1) * a->stride > (int64_t)a->T) {
+    rc_set_error("score_recording_pack: the last window ends at row %lld, past T=%d",
+                 (long long)a->start + (long long)(a->count - 1) * a->stride, a->T);
+    return REDCLIFF_EINVAL;
+  }
+  ScoreReps reps;
+  memset(&reps, 0, sizeof(reps));
+  reps.R = a->R;
+  if (a->replicas) {  // the rules of RedcliffStepArgs.replicas
+    if (a->n_replicas < 0 || a->n_replicas > a->R) {
+      rc_set_error("score_recording_pack: active replica list of %d entries (at most R=%d)", a->n_replicas, a->R);
+      return REDCLIFF_EINVAL;
+    }
+    for (int i = 0; i < a->n_replicas; ++i) {
+      const int r = a->replicas[i];
+      if (r < 0 || r >= a->R || (i > 0 && r <= a->replicas[i - 1])) {
+        rc_set_error("score_recording_pack: active replica list must be strictly increasing indices < R=%d (entry %d = %d)",
+                     a->R, i, r);
+        return REDCLIFF_EINVAL;
+      }
+      reps.rmap[i] = (uint8_t)r;
+    }
+    reps.nrep = a->n_replicas;
+    reps.rident = 0;
+  } else {
+    reps.nrep = a->R;
+    reps.rident = 1;
+  }
+  const ScoreWs o = score_ws(d);
+  if (a->ws_bytes < sizeof(float) * (size_t)o.total * (size_t)a->R) {
+    rc_set_error("score_recording_pack: workspace too small: %zu < %zu", a->ws_bytes,
+                 sizeof(float) * (size_t)o.total * (size_t)a->R);
+    return REDCLIFF_EWORKSPACE;
+  }
+  if (a->count == 0 || reps.nrep == 0) return 0;
+  reps.es = a->emb_stride; reps.bns = a->bn_stride; reps.xps = a->x_pstride; reps.wss = o.total;
+  hipStream_t s = (hipStream_t)stream;
+  float* ws = (float*)a->ws;
+  const EmbOff eo = rc_emb_off(d);
+  // every replica's supports in its slice of this call's workspace: one k_supports launch
+  RedcliffDims dR = d;
+  dR.R = a->R;
+  WsOff wo;
+  memset(&wo, 0, sizeof(wo));
+  wo.S = o.S;
+  if ((e = timed(KT_SUPPORTS, s, [&] { return rc_launch_supports(dR, a->emb, a->emb_stride, ws, o.total, eo, wo, s); })))
+    return e;
+  if ((e = timed(KT_SUPPORTS, s, [&] {
+         return rc_launch_score_tables(d, eo, a->emb, a->bn_rm, a->bn_rv, (float)a->bn_eps, ws + o.S, ws + o.Wf, ws + o.Zb, s,
+                                       &reps);
+       })))
+    return e;
+  if ((e = timed(KT_SCORE, s, [&] {
+         return rc_launch_score_windows(d, eo, a->emb, a->X, a->x_rstride, a->Nrec, a->start, a->count, a->stride,
+                                        a->use_final_activation, ws + o.S, ws + o.Wf, ws + o.Zb, a->w, a->logits, s, &reps);
+       })))
+    return e;
+  if (a->graphs &&
+      (e = timed(KT_SCORE_GRAPHS, s, [&] {
+         return rc_launch_score_graphs(a->w, a->tab, a->bias, a->graphs, d.K, a->Q, (int64_t)a->Nrec * a->count, s, &reps);
+       })))
+    return e;
+  return 0;
+}
+
 // ---- recording scoring of cEmbedder models (rc_score_cemb.hip) ----------------------------------
 // Only the embedder's dimensions play a part (Bmax, T, L, h, n, H, M1 are not read).
 static int cemb_score_dims(const RedcliffDims* d, int32_t eh) {

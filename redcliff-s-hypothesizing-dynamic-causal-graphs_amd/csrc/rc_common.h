@@ -763,13 +763,25 @@ bool rc_fac_mfma_fits(const RedcliffDims& d, bool cemb);
 // recording scoring (rc_score.hip): the LDS rows per (support, channel) a tile may stage (0: the
 // shape does not fit), the folded tables, the sliding-window embedder, the graph trace
 int rc_score_rows_budget(const RedcliffDims& d);
+// The replicas of a packed scoring launch (redcliff_score_recording_pack); a null ScoreReps* is
+// one replica with every stride 0 (redcliff_score_recording).
+struct ScoreReps {
+  int R;             // replicas of the per-replica buffers: the tables are built for all of them
+  int nrep, rident;  // scored replicas = rows of the outputs; rident: all R in order, else rmap
+  int64_t es, bns;   // replica strides (floats) of the embedder blocks / the running statistics
+  int64_t xps;       // ... of the recording sets (0: shared)
+  int64_t wss;       // ... of the workspace's S | Wf | Zb slices
+  uint8_t rmap[RC_MAX_ACTIVE];
+};
 int rc_launch_score_tables(const RedcliffDims& d, const EmbOff& eo, const float* emb, const float* rm, const float* rv,
-                           float bn_eps, const float* S, float* Wf, float* Zb, hipStream_t s);
+                           float bn_eps, const float* S, float* Wf, float* Zb, hipStream_t s,
+                           const ScoreReps* reps = nullptr);
 int rc_launch_score_windows(const RedcliffDims& d, const EmbOff& eo, const float* emb, const float* X, int64_t xrs,
                             int Nrec, int start, int count, int stride, int ufa, const float* S, const float* Wf,
-                            const float* Zb, float* w, float* logits, hipStream_t s);
+                            const float* Zb, float* w, float* logits, hipStream_t s, const ScoreReps* reps = nullptr);
+// w / out rows of nwin windows per scored replica, tab[R][K][Q] / bias[R][Q] indexed by replica
 int rc_launch_score_graphs(const float* w, const float* tab, const float* bias, float* out, int K, int Q, int64_t nwin,
-                           hipStream_t s);
+                           hipStream_t s, const ScoreReps* reps = nullptr);
 // recording scoring of cEmbedder models (rc_score_cemb.hip): the LDS rows per channel a tile may
 // stage (0: outside the kernel's limits) and the sliding-window embedder
 int rc_score_cemb_rows_budget(const RedcliffDims& d, int eh);

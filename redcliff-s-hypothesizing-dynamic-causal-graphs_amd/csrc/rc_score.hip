@@ -25,6 +25,15 @@
 // A wave owns the (channel, 16-column) items wv, wv + 4, ... in ascending order and accumulates its
 // own fc1 partial; the four partials are summed in wave order.  Nothing depends on the tile's
 // position, count, stride or Nrec, so a window's bits do not either.  No atomics, no scratch.
+//
+// Packs (redcliff_score_recording_pack): the same kernels with the replica on a grid axis.  A
+// workgroup of replica r reads r's embedder block, tables and recordings through replica strides
+// and writes row i of the outputs, i the replica's place in the active list; everything after the
+// base pointers is the single-model code, so a window's bits depend on the dims alone -- not on R,
+// the replica's index, the active list or whether the recordings are shared.  The single-model
+// entry is the pack of one replica with all strides 0.
+#include <cstring>
+
 #include "rc_common.h"
 
 #define SC_TW 16        // windows per tile (MFMA rows)
@@ -35,8 +44,10 @@
 struct ScoreCtx {
   RedcliffDims d;
   EmbOff eo;
-  const float* emb;
-  const float* X; int64_t xrs;  // recording stride (floats)
+  const float* emb; int64_t es;  // replica stride of the embedder blocks (floats)
+  const float* X; int64_t xrs;   // recording stride (floats)
+  int64_t xps;                   // replica stride of the recording sets (0: shared)
+  int64_t wss;                   // replica stride of S / Wf / Zb (the call's workspace)
   int start, count, stride;
   int tw;     // scored steps per tile (<= SC_TW; fewer when the stride spreads a tile's rows too far)
   int rowsP;  // LDS rows per (support, channel)
@@ -44,18 +55,26 @@ struct ScoreCtx {
   const float* S;   // [n][p][p]
   const float* Wf;  // [n][F][H]
   const float* Zb;  // [p][H]
-  float* w;         // [Nrec][count][K]
-  float* logits;    // [Nrec][count][nsup] or null
+  float* w;         // [nrep][Nrec][count][K]
+  float* logits;    // [nrep][Nrec][count][nsup] or null
+  // blockIdx.z = i-th active replica: replica rmap[i], or i when rident (as StepCtx)
+  int rident;
+  uint8_t rmap[RC_MAX_ACTIVE];
 };
 
 namespace {
 
-// Folded tables of one call.  grid (ceil(max(n F H, p H) / 256)).
-__global__ __launch_bounds__(RC_BLOCK) void k_score_tables(RedcliffDims d, EmbOff eo, const float* emb, const float* rm,
-                                                           const float* rv, float bn_eps, const float* S, float* Wf,
-                                                           float* Zb) {
+// Folded tables of one call.  grid (ceil(max(n F H, p H) / 256), R): replica blockIdx.y reads its
+// embedder block (stride es), running statistics (stride bns) and supports, and writes its tables
+// (stride wss).
+__global__ __launch_bounds__(RC_BLOCK) void k_score_tables(RedcliffDims d, EmbOff eo, const float* emb, int64_t es,
+                                                           const float* rm, const float* rv, int64_t bns, float bn_eps,
+                                                           const float* S, float* Wf, float* Zb, int64_t wss) {
   const int p = d.p, F = d.F, H = d.H, n = d.n;
   const int e = blockIdx.x * RC_BLOCK + threadIdx.x;
+  const int64_t rep = blockIdx.y;
+  emb += rep * es; rm += rep * bns; rv += rep * bns;
+  S += rep * wss; Wf += rep * wss; Zb += rep * wss;
   const float* W = emb + eo.gcW;
   // torch batch_norm in eval mode: y = x * alpha + beta
   auto alpha = [&](int f) { return (1.0f / sqrtf(rv[f] + bn_eps)) * emb[eo.bnw + f]; };
@@ -83,7 +102,7 @@ __global__ __launch_bounds__(RC_BLOCK) void k_score_tables(RedcliffDims d, EmbOf
   }
 }
 
-// grid (tiles, Nrec), 256 threads.  Dynamic LDS: Yl[n][p][rowsP] | Wl[n F][H] | relu tiles
+// grid (tiles, Nrec, active replicas), 256 threads.  Dynamic LDS: Yl[n][p][rowsP] | Wl[n F][H] | relu tiles
 // [4][16][SC_RP]; the first SC_TAIL_FLOATS are reused by the fc1 / fc2 tail.
 __global__ __launch_bounds__(RC_BLOCK) void k_score_windows(ScoreCtx c) {
   extern __shared__ float sm[];
@@ -98,8 +117,13 @@ __global__ __launch_bounds__(RC_BLOCK) void k_score_windows(ScoreCtx c) {
   if (nw <= 0) return;
   const int nrows = (nw - 1) * c.stride + F;  // <= rowsP (host)
   // first row of the tile: >= 0 (start >= F); last row start + (j0 + nw - 1) stride - 1 < T (host)
-  const float* Xr = c.X + (int64_t)r * c.xrs + ((int64_t)c.start + (int64_t)j0 * c.stride - F) * p;
-  const float* E = c.emb;
+  const int ri = blockIdx.z;                                     // row of the outputs
+  const int64_t rep = c.rident ? ri : (int)c.rmap[ri];           // replica
+  const float* Xr = c.X + rep * c.xps + (int64_t)r * c.xrs + ((int64_t)c.start + (int64_t)j0 * c.stride - F) * p;
+  const float* E = c.emb + rep * c.es;
+  const float* Sg = c.S + rep * c.wss;
+  const float* Wfg = c.Wf + rep * c.wss;
+  const float* Zbg = c.Zb + rep * c.wss;
 
   float* Yl = sm;                       // [n][p][rowsP]
   float* Wl = Yl + n * p * rowsP;       // [nF][H]
@@ -109,13 +133,13 @@ __global__ __launch_bounds__(RC_BLOCK) void k_score_windows(ScoreCtx c) {
     const int row = e / p, ch = e - row * p;
     Yl[ch * rowsP + row] = Xr[e];
   }
-  for (int e = tid; e < nF * H; e += RC_BLOCK) Wl[e] = c.Wf[e];
+  for (int e = tid; e < nF * H; e += RC_BLOCK) Wl[e] = Wfg[e];
   __syncthreads();
   // Y_i = S_i X for i >= 1, once per staged row (row fastest: a wave reads one S row at a time)
   for (int e = tid; e < (n - 1) * p * nrows; e += RC_BLOCK) {
     const int rem = e / nrows, row = e - rem * nrows;
     const int i1 = rem / p, ch = rem - i1 * p;
-    const float* Srow = c.S + ((int64_t)(i1 + 1) * p + ch) * p;
+    const float* Srow = Sg + ((int64_t)(i1 + 1) * p + ch) * p;
     float v = 0.f;
     for (int cc = 0; cc < p; ++cc) v += Srow[cc] * Yl[cc * rowsP + row];
     Yl[((i1 + 1) * p + ch) * rowsP + row] = v;
@@ -155,7 +179,7 @@ __global__ __launch_bounds__(RC_BLOCK) void k_score_windows(ScoreCtx c) {
       f += 4;
       while (f >= F) { f -= F; ++i; }
     }
-    const float zb = col ? c.Zb[ch * H + hh0 + l15] : 0.f;
+    const float zb = col ? Zbg[ch * H + hh0 + l15] : 0.f;
     __builtin_amdgcn_wave_barrier();  // the previous item's tile reads are done
 #pragma unroll
     for (int q = 0; q < 4; ++q) Rt[(4 * g + q) * SC_RP + l15] = fmaxf(acc[q] + zb, 0.f);
@@ -192,20 +216,32 @@ __global__ __launch_bounds__(RC_BLOCK) void k_score_windows(ScoreCtx c) {
     float a = 0.f;
     for (int m = 0; m < M1; ++m) a += w2[m] * f1l[s * 64 + m];
     const float raw = a + E[c.eo.fc2b + k];
-    const int64_t win = (int64_t)r * c.count + j0 + s;
+    const int64_t win = ((int64_t)ri * gridDim.y + r) * c.count + j0 + s;
     c.w[win * K + k] = d.use_sigmoid ? rc_sigmoid(d.sigmoid_ecc * raw) : raw;
     if (k < nsup && c.logits) c.logits[win * nsup + k] = (d.use_sigmoid && c.ufa) ? rc_sigmoid(raw) : raw;
   }
 }
 
 // Graph trace: out[win][q] = bias[q] + sum_k w[win][k] tab[k][q], k ascending.  One workgroup per 16
-// consecutive windows of the flattened [Nrec * count] axis.
+// consecutive windows of the flattened [Nrec * count] axis of one output row; grid (blocks, rows).
+// Row i holds the i-th active replica, which reads its own tab[K][Q] / bias[Q] (replica stride
+// K Q / Q; the single-model call is one row of replica 0).
+struct GraphReps {
+  int rident;
+  uint8_t rmap[RC_MAX_ACTIVE];
+};
 __global__ __launch_bounds__(RC_BLOCK) void k_score_graphs(const float* w, const float* tab, const float* bias, float* out,
-                                                           int K, int Q, int64_t nwin) {
+                                                           int K, int Q, int64_t nwin, GraphReps gr) {
   __shared__ float wl[SC_TW * 16];
   const int64_t w0 = (int64_t)blockIdx.x * SC_TW;
   const int nw = (int)min((int64_t)SC_TW, nwin - w0);
   if (nw <= 0) return;
+  const int ri = blockIdx.y;
+  const int64_t rep = gr.rident ? ri : (int)gr.rmap[ri];
+  w += (int64_t)ri * nwin * K;
+  out += (int64_t)ri * nwin * Q;
+  tab += rep * K * Q;
+  if (bias) bias += rep * Q;
   for (int e = threadIdx.x; e < nw * K; e += RC_BLOCK) wl[e] = w[w0 * K + e];
   __syncthreads();
   for (int q = threadIdx.x; q < Q; q += RC_BLOCK) {
@@ -229,22 +265,33 @@ int rc_score_rows_budget(const RedcliffDims& d) {
 }
 
 int rc_launch_score_tables(const RedcliffDims& d, const EmbOff& eo, const float* emb, const float* rm, const float* rv,
-                           float bn_eps, const float* S, float* Wf, float* Zb, hipStream_t s) {
+                           float bn_eps, const float* S, float* Wf, float* Zb, hipStream_t s, const ScoreReps* reps) {
   const int nE = d.n * d.F * d.H > d.p * d.H ? d.n * d.F * d.H : d.p * d.H;
-  hipLaunchKernelGGL(k_score_tables, dim3((nE + RC_BLOCK - 1) / RC_BLOCK), dim3(RC_BLOCK), 0, s, d, eo, emb, rm, rv, bn_eps,
-                     S, Wf, Zb);
+  const int R = reps ? reps->R : 1;
+  hipLaunchKernelGGL(k_score_tables, dim3((nE + RC_BLOCK - 1) / RC_BLOCK, R), dim3(RC_BLOCK), 0, s, d, eo, emb,
+                     reps ? reps->es : 0, rm, rv, reps ? reps->bns : 0, bn_eps, S, Wf, Zb, reps ? reps->wss : 0);
   return rc_check(hipGetLastError(), "k_score_tables");
 }
 
 int rc_launch_score_windows(const RedcliffDims& d, const EmbOff& eo, const float* emb, const float* X, int64_t xrs,
                             int Nrec, int start, int count, int stride, int ufa, const float* S, const float* Wf,
-                            const float* Zb, float* w, float* logits, hipStream_t s) {
+                            const float* Zb, float* w, float* logits, hipStream_t s, const ScoreReps* reps) {
   const int budget = rc_score_rows_budget(d);
   if (budget <= 0) { rc_set_error("score_recording: LDS budget exceeded"); return REDCLIFF_ELIMIT; }
   ScoreCtx c;
+  memset(&c, 0, sizeof(c));
   c.d = d; c.eo = eo; c.emb = emb; c.X = X; c.xrs = xrs;
   c.start = start; c.count = count; c.stride = stride; c.ufa = ufa;
   c.S = S; c.Wf = Wf; c.Zb = Zb; c.w = w; c.logits = logits;
+  c.rident = 1;
+  int nrep = 1;
+  if (reps) {
+    c.es = reps->es; c.xps = reps->xps; c.wss = reps->wss;
+    c.rident = reps->rident;
+    nrep = reps->nrep;
+    if (nrep < 1 || nrep > RC_MAX_ACTIVE) { rc_set_error("score_recording: %d active replicas", nrep); return REDCLIFF_ELIMIT; }
+    memcpy(c.rmap, reps->rmap, sizeof(c.rmap));
+  }
   // as many steps per tile as the staged span allows (the arithmetic of a window does not depend on it)
   int tw = SC_TW;
   if ((int64_t)(SC_TW - 1) * stride + d.F > budget) tw = (int)(((int64_t)budget - d.F) / stride) + 1;
@@ -259,14 +306,24 @@ int rc_launch_score_windows(const RedcliffDims& d, const EmbOff& eo, const float
   if (Nrec > 65535 || tiles > 0x7fffffff) { rc_set_error("score_recording: grid too large (Nrec <= 65535)"); return REDCLIFF_ELIMIT; }
   int e = rc_lds_optin(k_score_windows, lds, "k_score_windows LDS");
   if (e) return e;
-  hipLaunchKernelGGL(k_score_windows, dim3((unsigned)tiles, Nrec), dim3(RC_BLOCK), lds, s, c);
+  hipLaunchKernelGGL(k_score_windows, dim3((unsigned)tiles, Nrec, nrep), dim3(RC_BLOCK), lds, s, c);
   return rc_check(hipGetLastError(), "k_score_windows");
 }
 
 int rc_launch_score_graphs(const float* w, const float* tab, const float* bias, float* out, int K, int Q, int64_t nwin,
-                           hipStream_t s) {
+                           hipStream_t s, const ScoreReps* reps) {
   const int64_t nb = (nwin + SC_TW - 1) / SC_TW;
   if (nb > 0x7fffffff) { rc_set_error("score_recording: too many windows for the graph trace"); return REDCLIFF_ELIMIT; }
-  hipLaunchKernelGGL(k_score_graphs, dim3((unsigned)nb), dim3(RC_BLOCK), 0, s, w, tab, bias, out, K, Q, nwin);
+  GraphReps gr;
+  memset(&gr, 0, sizeof(gr));
+  gr.rident = 1;
+  int nrep = 1;
+  if (reps) {
+    gr.rident = reps->rident;
+    nrep = reps->nrep;
+    if (nrep < 1 || nrep > RC_MAX_ACTIVE) { rc_set_error("score_recording: %d active replicas", nrep); return REDCLIFF_ELIMIT; }
+    memcpy(gr.rmap, reps->rmap, sizeof(gr.rmap));
+  }
+  hipLaunchKernelGGL(k_score_graphs, dim3((unsigned)nb, nrep), dim3(RC_BLOCK), 0, s, w, tab, bias, out, K, Q, nwin, gr);
   return rc_check(hipGetLastError(), "k_score_graphs");
 }

@@ -42,7 +42,8 @@ EXPORTED = ("redcliff_abi_version", "redcliff_last_error", "redcliff_workspace_b
             "redcliff_cemb_param_count", "redcliff_cemb_workspace_bytes", "redcliff_cemb_workspace_regions",
             "redcliff_cemb_train_step", "redcliff_cemb_train_steps",
             "redcliff_score_recording_workspace_bytes", "redcliff_score_recording",
-            "redcliff_cemb_score_supported", "redcliff_cemb_score_recording")
+            "redcliff_cemb_score_supported", "redcliff_cemb_score_recording",
+            "redcliff_score_recording_pack_workspace_bytes", "redcliff_score_recording_pack")
 CEMB_WS_REGIONS = ("ha", "w1", "g", "g0", "E", "E0", "dE", "draw")
 KERNEL_IDS = ("supports", "emb_fwd", "fac_fwd", "fac_bwd", "emb_bwd", "emb_final", "fac_mix", "emb_combine", "fac_lead",
               "score", "score_graphs", "score_cemb")
@@ -96,6 +97,17 @@ class ScoreArgs(ctypes.Structure):
                 ("use_final_activation", ctypes.c_int32), ("w", _vp), ("logits", _vp),
                 ("tab", _vp), ("bias", _vp), ("graphs", _vp), ("Q", ctypes.c_int32), ("pad_", ctypes.c_int32),
                 ("ws", _vp), ("ws_bytes", ctypes.c_size_t)]
+
+
+class ScorePackArgs(ctypes.Structure):
+    """RedcliffScorePackArgs (redcliff_score_recording_pack)."""
+    _fields_ = [("d", Dims), ("R", ctypes.c_int32), ("pad0_", ctypes.c_int32), ("emb", _vp), ("emb_stride", _i64),
+                ("bn_rm", _vp), ("bn_rv", _vp), ("bn_stride", _i64), ("bn_eps", ctypes.c_double),
+                ("X", _vp), ("x_rstride", _i64), ("x_pstride", _i64), ("Nrec", ctypes.c_int32), ("T", ctypes.c_int32),
+                ("start", ctypes.c_int32), ("count", ctypes.c_int32), ("stride", ctypes.c_int32),
+                ("use_final_activation", ctypes.c_int32), ("w", _vp), ("logits", _vp),
+                ("tab", _vp), ("bias", _vp), ("graphs", _vp), ("Q", ctypes.c_int32), ("n_replicas", ctypes.c_int32),
+                ("replicas", _vp), ("ws", _vp), ("ws_bytes", ctypes.c_size_t)]
 
 
 class CEmbScoreArgs(ctypes.Structure):
@@ -173,14 +185,18 @@ def lib():
     L.redcliff_score_recording.argtypes = [ctypes.POINTER(ScoreArgs), _vp]
     L.redcliff_cemb_score_supported.argtypes = [ctypes.POINTER(Dims), ctypes.c_int32]
     L.redcliff_cemb_score_recording.argtypes = [ctypes.POINTER(CEmbScoreArgs), _vp]
+    L.redcliff_score_recording_pack_workspace_bytes.argtypes = [ctypes.POINTER(Dims), ctypes.c_int32]
+    L.redcliff_score_recording_pack.argtypes = [ctypes.POINTER(ScorePackArgs), _vp]
     for name in EXPORTED[2:]:
         if name not in ("redcliff_workspace_bytes", "redcliff_emb_param_count", "redcliff_fac_param_count",
                         "redcliff_build_id", "redcliff_cemb_param_count", "redcliff_cemb_workspace_bytes",
-                        "redcliff_score_recording_workspace_bytes"):
+                        "redcliff_score_recording_workspace_bytes",
+                        "redcliff_score_recording_pack_workspace_bytes"):
             getattr(L, name).restype = ctypes.c_int
     L.redcliff_cemb_param_count.restype = ctypes.c_size_t
     L.redcliff_cemb_workspace_bytes.restype = ctypes.c_size_t
     L.redcliff_score_recording_workspace_bytes.restype = ctypes.c_size_t
+    L.redcliff_score_recording_pack_workspace_bytes.restype = ctypes.c_size_t
     L.redcliff_build_id.restype = ctypes.c_char_p
     if L.redcliff_abi_version() != ABI_VERSION:
         raise ImportError("libredcliff_hip.so ABI %d != %d" % (L.redcliff_abi_version(), ABI_VERSION))

@@ -460,6 +460,62 @@ class ReplicaPack:
                                               ctypes.c_void_p(G0.data_ptr()), _stream()), "packed gc_norms")
         return G, G0
 
+    @staticmethod
+    def _embedder_bound(e):
+        """The embedder's parameters and BatchNorm statistics of engine e still alias its pack row."""
+        bn = e.dgcnn.BN1
+        ptrs = e.bound_ptrs
+        return (all(q.data_ptr() == ptrs[i] for i, q in enumerate(e.group_params["A"]))
+                and bn.running_mean.data_ptr() == e.bn[0].data_ptr() and bn.running_var.data_ptr() == e.bn[1].data_ptr())
+
+    def score_recording(self, X, start=None, count=None, stride=1, use_final_activation=True, graphs=None,
+                        gc_est_mode=None, ignore_lag=True, active=None):
+        """model.score_recording for the pack's replicas in one launch chain (scoring.score_recordings
+        reading the pack's rows in place): RecordingScores with a leading axis over the active replicas
+        in ascending order (all when None), row i bit for bit what that model's own call gives.
+        X: (T, p) / (Nrec, T, p) shared, or per replica -- a PerReplica list of R tensors or an
+        (R, Nrec, T, p) tensor, indexed by replica whatever `active` says.  The kernels read self.emb
+        and self.bn; the graph tables of all replicas come from one gc_norms launch; the workspace is
+        the call's own.  Inference only: the pack's workspace and supports, BatchNorm statistics,
+        step counts and the module modes are left alone."""
+        from . import scoring
+        R, models, e0 = self.R, self.models, self.engines[0]
+        modes = [scoring._graph_mode(m, graphs, gc_est_mode) for m in models]
+        Xn, per_replica, s0, c0, st = scoring._pack_window_args(models[0], X, R, start, count, stride)
+        idx = scoring._active_indices(active, R)
+        eps = set(float(e.dgcnn.BN1.eps) for e in self.engines)
+        # one shape: the library's answer for replica 0 holds for all of them
+        fused = all(m.wavelet_level is None and m.fused_supported() for m in models) and scoring.fused_available(models[0])
+        if len(eps) != 1 or len(set(modes)) != 1 or not fused:
+            # wavelet models, mixed BatchNorm eps: model by model
+            parts = [models[r].score_recording(Xn[r] if per_replica else Xn, start, count, stride, use_final_activation,
+                                               graphs, gc_est_mode, ignore_lag) for r in idx]
+            if not parts:  # nothing active: empty tensors of the shapes a row would have
+                def none(*tail):
+                    return torch.empty((0, Xn.shape[-3], c0) + tuple(tail), device=self.device, dtype=torch.float32)
+                gs = None
+                if modes[0] is not None:
+                    with torch.no_grad():
+                        gs = none(*scoring.graph_tables(models[0], modes[0], ignore_lag)[0].shape[1:])
+                return scoring.RecordingScores(none(e0.K), none(e0.nsup) if e0.nsup > 0 else None, gs)
+            return scoring._stack_scores(parts, "ReplicaPack.score_recording")
+        mode = modes[0]
+        # the kernels read self.emb and self.bn (and, for the tables, self.fac): without a graph trace
+        # only the embedder groups' addresses are compared, R * (7 + n) of them instead of every
+        # parameter's -- the call's host time is all spent before its first launch
+        if mode is not None or not all(self._embedder_bound(e) for e in self.engines):
+            self._ensure_bound()
+        with torch.no_grad():
+            tab = bias = None
+            if mode is not None:
+                G, G0 = self.gc_norms()
+                A = self.emb[:, :e0.p * e0.p].view(R, e0.p, e0.p)
+                tab, bias = scoring.pack_graph_tables(G, G0, A, mode, ignore_lag, min(e0.L, e0.F))
+            return scoring.RecordingScores(*scoring.pack_launch(
+                scoring._score_dims(models[0]), R, self.emb, self.emb.shape[1], self.bn[0], self.bn[1], self.bn.shape[2],
+                eps.pop(), Xn, per_replica, s0, c0, st, use_final_activation, tab, bias,
+                None if active is None else idx))
+
     # ------------------------------------------------------------------ packed fit
     def fit(self, *args, **kwargs):
         """R fits of ``fit()`` in one packed launch chain; see ``_fit``.  The host side of an epoch
