@@ -449,6 +449,51 @@ typedef struct RedcliffCEmbScoreArgs {
 int redcliff_cemb_score_supported(const RedcliffDims* d, int32_t eh);
 int redcliff_cemb_score_recording(const RedcliffCEmbScoreArgs* a, void* stream);
 
+/* ---- the cMLP forecasting baseline cMLP_FM (models/cmlp_fm.py:96-201, 419-475) ----
+ * Purely additive entries: REDCLIFF_ABI_VERSION stays 10, no existing entry or layout changes.
+ *
+ * The model is one cMLP (K = 1) with no embedder; its loss is c_forecast * sum_i MSE(pred[:, :, i],
+ * target[:, :, i]) + c_adj * sum ||GC(ignore_lag=True)||_1 (models/cmlp_fm.py:156-178), one Adam.
+ * The loss separates over the p channel networks, so one launch on grid (p, stepped replicas) runs
+ * nsteps = ceil(N / B) consecutive batch_updates (:180-201) of the windows X[row0 + i*B ...] (the
+ * last batch may be ragged): workgroup (j, r) keeps network j's weights and Adam moments in LDS for
+ * the whole call and writes them back once.  Window rows [0, L) are the input, row L the target
+ * (num_sims == 1, output_length == 1, input_length == gen_lag, no wavelets).  Per step i:
+ *   z[b][u] = b0[u] + sum_q W0[u][q] X[row+b][t][c]  (q = c*L + t ascending)   a = relu(z)
+ *   y[b] = b1 + sum_u W1[u] a[b][u]      res[b] = y[b] - X[row+b][L][j]
+ *   dy[b] = c_forecast * (2 / B_i) * res[b]                       (RC_LOSS_FORECAST)
+ *   dW0[u][c][t] += c_adj * W0[u][c][t] / G0[c]                   (RC_LOSS_ADJ; 0 where G0[c] == 0)
+ *   Adam of hyper[r].B at step number tB + i                      (RC_STEP_B)
+ * Outputs: sse[i'][i][j] = sum_b res[b]^2 and, with RC_VALUES, pen[i'][i][j] = sum_c G0[c] at the
+ * weights step i used (i' = the i'-th stepped replica in ascending order); when G / G0 are given,
+ * G[r][j][c][t] / G0[r][j][c] of the final weights in redcliff_gc_norms' layout (indexed by replica).
+ * Without RC_STEP_B the call is the batch body of validate_training (:419-475): parameters and
+ * moments are only read.  Replica r reads X + r*x_pstride (0: all replicas fit the same set) and its
+ * factor block at fac + r*fac_stride (layout above at K = 1; fac_m / fac_v alike).
+ * Limits: K == 1, p <= 64, h <= 128, Bmax <= 512, T >= L + 1, R <= 256 and
+ *   4*h*Qp + 3*(2h + 1) + 64*(Qp + hp + 2) + p*L + p + 8 <= 40960 floats of LDS  (Qp = p*L | 1, hp = h | 1);
+ * outside them REDCLIFF_ELIMIT.  Null buffers, flags outside the four above, B < 1 or > Bmax, N < 0,
+ * a bad active list, negative strides: REDCLIFF_EINVAL.  N == 0 or an empty list launches nothing.
+ * All checks precede any HIP call.  Stream-ordered, no atomics, every sum in an order fixed by
+ * (p, L, h) and the batch size: a replica's bits do not depend on R, the active list, or on how
+ * [row0, row0 + N) is split into calls at multiples of B. */
+typedef struct RedcliffFMArgs {
+  RedcliffDims d;            /* R, Bmax, T, p, L, h read; K must be 1; the embedder fields are ignored */
+  int32_t flags;             /* RC_LOSS_FORECAST | RC_LOSS_ADJ | RC_STEP_B | RC_VALUES             */
+  int32_t B, tB;             /* batch size; Adam step number of the first step (1-based)            */
+  int64_t row0, N;           /* windows [row0, row0 + N) in batches of B                             */
+  const float* X; int64_t x_pstride;
+  float* fac; float* fac_m; float* fac_v; int64_t fac_stride;
+  const RedcliffReplicaHyper* hyper;        /* device [R]: c_forecast, c_adj, B (Adam) read          */
+  float* sse; float* pen;    /* [n stepped][nsteps][p]; pen may be NULL without RC_VALUES            */
+  float* G; float* G0;       /* optional final norms [R][p][p][L] / [R][p][p], may be NULL           */
+  const int32_t* replicas; int32_t n_replicas;   /* as RedcliffStepArgs.replicas                    */
+} RedcliffFMArgs;
+/* Host-only limit query: 0 outside the limits (with a redcliff_last_error message), else the
+ * workgroup's LDS footprint in floats. */
+int redcliff_fm_supported(const RedcliffDims* d);
+int redcliff_fm_run(const RedcliffFMArgs* a, void* stream);
+
 /* Per-kernel HIP-event timing for benchmarking: redcliff_kernel_timing(1) brackets every
  * kernel launched by redcliff_train_step with events on its stream; redcliff_kernel_times()
  * synchronises them and returns per-kernel totals (ids 0..11: supports, emb_fwd, fac_fwd,

@@ -6,6 +6,7 @@
 #include <vector>
 
 #include "rc_common.h"
+#include "rc_fm.h"
 
 // ---- optional per-kernel HIP-event timing (bench / profiling only) -------------------------
 namespace {
@@ -868,6 +869,84 @@ int redcliff_cemb_score_recording(const RedcliffCEmbScoreArgs* a, void* stream) 
        })))
     return e;
   return 0;
+}
+
+// ---- the cMLP_FM baseline (rc_fm.hip) ----------------------------------------------------------
+static int fm_dims(const RedcliffDims* d) {
+  if (!d) { rc_set_error("null dims"); return REDCLIFF_EINVAL; }
+  if (d->R < 1 || d->Bmax < 1 || d->T < 1 || d->p < 1 || d->L < 1 || d->K < 1 || d->h < 1) {
+    rc_set_error("invalid dims (R=%d Bmax=%d T=%d p=%d L=%d K=%d h=%d)", d->R, d->Bmax, d->T, d->p, d->L, d->K, d->h);
+    return REDCLIFF_EINVAL;
+  }
+  if (d->K != 1 || d->p > 64 || d->h > 128 || d->Bmax > 512 || d->T < d->L + 1 || d->R > RC_MAX_ACTIVE ||
+      (int64_t)d->p * d->L > RC_LDS_MAX_FLOATS || rc_fm_lds_floats(d->p, d->L, d->h) > RC_LDS_MAX_FLOATS) {
+    rc_set_error("dims outside kernel limits (fm: K==1 p<=64 h<=128 Bmax<=512 T>=L+1 R<=%d, LDS 4*h*Qp + 3*(2h+1) + "
+                 "64*(Qp+hp+2) + p*L + p + 8 <= %d floats; p=%d L=%d h=%d K=%d Bmax=%d T=%d R=%d)", RC_MAX_ACTIVE,
+                 RC_LDS_MAX_FLOATS, d->p, d->L, d->h, d->K, d->Bmax, d->T, d->R);
+    return REDCLIFF_ELIMIT;
+  }
+  return 0;
+}
+
+int redcliff_fm_supported(const RedcliffDims* d) {
+  if (fm_dims(d) != 0) return 0;
+  return (int)rc_fm_lds_floats(d->p, d->L, d->h);
+}
+
+int redcliff_fm_run(const RedcliffFMArgs* a, void* stream) {
+  if (!a) { rc_set_error("null fm arguments"); return REDCLIFF_EINVAL; }
+  int e = fm_dims(&a->d);
+  if (e) return e;
+  const RedcliffDims& d = a->d;
+  if (a->flags & ~(RC_LOSS_FORECAST | RC_LOSS_ADJ | RC_STEP_B | RC_VALUES)) {
+    rc_set_error("fm_run: unsupported flags 0x%x", a->flags);
+    return REDCLIFF_EINVAL;
+  }
+  if (!a->X || !a->fac || !a->hyper || !a->sse || ((a->flags & RC_VALUES) && !a->pen) ||
+      ((a->flags & RC_STEP_B) && (!a->fac_m || !a->fac_v))) {
+    rc_set_error("fm_run: null buffer in arguments");
+    return REDCLIFF_EINVAL;
+  }
+  if (a->B < 1 || a->B > d.Bmax || a->N < 0 || a->row0 < 0 || a->tB < 1) {
+    rc_set_error("fm_run: bad arguments (B=%d (1..Bmax=%d) N=%lld row0=%lld tB=%d)", a->B, d.Bmax, (long long)a->N,
+                 (long long)a->row0, a->tB);
+    return REDCLIFF_EINVAL;
+  }
+  if (a->x_pstride < 0 || a->fac_stride < 0) {
+    rc_set_error("fm_run: negative replica stride (x_pstride=%lld fac_stride=%lld)", (long long)a->x_pstride,
+                 (long long)a->fac_stride);
+    return REDCLIFF_EINVAL;
+  }
+  const int64_t nsteps = (a->N + a->B - 1) / a->B;
+  if (nsteps > INT32_MAX) { rc_set_error("fm_run: too many steps"); return REDCLIFF_ELIMIT; }
+  FmCtx c;
+  memset(&c, 0, sizeof(c));
+  if (a->replicas) {  // the rules of RedcliffStepArgs.replicas
+    if (a->n_replicas < 0 || a->n_replicas > d.R) {
+      rc_set_error("fm_run: active replica list of %d entries (at most R=%d)", a->n_replicas, d.R);
+      return REDCLIFF_EINVAL;
+    }
+    for (int i = 0; i < a->n_replicas; ++i) {
+      const int r = a->replicas[i];
+      if (r < 0 || r >= d.R || (i > 0 && r <= a->replicas[i - 1])) {
+        rc_set_error("fm_run: active replica list must be strictly increasing indices < R=%d (entry %d = %d)", d.R, i, r);
+        return REDCLIFF_EINVAL;
+      }
+      c.rmap[i] = (uint8_t)r;
+    }
+    c.nrep = a->n_replicas;
+    c.rident = 0;
+  } else {
+    c.nrep = d.R;
+    c.rident = 1;
+  }
+  if (a->N == 0 || c.nrep == 0) return 0;
+  c.p = d.p; c.L = d.L; c.h = d.h; c.T = d.T; c.B = a->B; c.flags = a->flags; c.tB = a->tB; c.nsteps = (int)nsteps;
+  c.row0 = a->row0; c.N = a->N; c.xps = a->x_pstride; c.fs = a->fac_stride;
+  c.X = a->X; c.fac = a->fac; c.facM = a->fac_m; c.facV = a->fac_v; c.hyp = a->hyper;
+  c.sse = a->sse; c.pen = a->pen; c.G = a->G; c.G0 = a->G0;
+  c.fo = rc_fac_off(d);
+  return rc_launch_fm(c, (hipStream_t)stream);
 }
 
 // Per-kernel timing: while enabled every launch of redcliff_train_step is bracketed by
