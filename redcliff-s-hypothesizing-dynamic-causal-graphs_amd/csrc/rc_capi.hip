@@ -424,14 +424,15 @@ int redcliff_train_step(const RedcliffStepArgs* a, void* stream) {
     if (fork && (e = stream_wait(s, sf, aux->ev[0]))) return e;
   }
   if ((fl & RC_VALUES) && (e = rc_launch_cos_values(c, s))) return e;  // before the head workgroup
-  // k_emb_combine + k_emb_final as one launch (k_emb_tail) when its grid is resident: the
-  // adjacency chain starts with the combine instead of after it, and one kernel boundary goes.
-  // REDCLIFF_TAIL=0 keeps the two launches.
+  // k_emb_combine + k_emb_final as one launch (k_emb_tail: every workgroup sums the window-block
+  // partials it needs in place, none waits for another) for single fits, while the adjacency
+  // workgroup's in-place dS sum stays short (rc_emb_tail_adj_rounds: D4IC, C1(K=4); not TST).
+  // REDCLIFF_TAIL=0 keeps the two launches, REDCLIFF_TAIL=1 takes the tail wherever it can run.
   const char* tlv = getenv("REDCLIFF_TAIL");
   bool tail = false;
   auto tail_ok = [&]() {
     return !egemm && emb_grad && c.defer == 1 && !(fl & RC_VALUES) && !(tlv && strcmp(tlv, "0") == 0) &&
-           rc_emb_tail_grid(c) > 0;
+           rc_emb_tail_grid(c) > 0 && ((tlv && strcmp(tlv, "1") == 0) || rc_emb_tail_adj_rounds(c) <= 2);
   };
   if (emb_grad && egemm) {
     // GEMM chain, then the fused kernel without node workgroups (head / adjacency-L1 reduce)

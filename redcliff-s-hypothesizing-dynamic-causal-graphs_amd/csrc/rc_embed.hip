@@ -870,8 +870,7 @@ __device__ __forceinline__ void emb_bwd_node(const StepCtx& c, int r, int node, 
 // (node, chunk) group blockIdx.y summed over the window blocks in block order and scattered
 // exactly as the last arriver does, so both variants give the same bits.
 // grid (ceil(pstride / RC_BLOCK), p * nchunk, R).
-// (emb_combine_elem: element e of group grp of replica r; sc1: coherent stores, read inside the
-// same launch by k_emb_tail's parameter workgroups)
+// (emb_combine_elem: element e of group grp of replica r)
 __device__ __forceinline__ bool emb_combine_in(const StepCtx& c, int grp, int e) {
   const RedcliffDims& d = c.d;
   const int ofs_h = d.M1 * EMB_HC + d.n * d.F * EMB_HC + (d.n - 1) * d.p + 2 * d.F;
@@ -893,7 +892,7 @@ __device__ __forceinline__ float emb_combine_sum(const StepCtx& c, int r, int gr
   }
   return t;
 }
-__device__ __forceinline__ void emb_combine_store(const StepCtx& c, int r, int grp, int e, float t, bool sc1) {
+__device__ __forceinline__ void emb_combine_store(const StepCtx& c, int r, int grp, int e, float t) {
   const RedcliffDims& d = c.d;
   if (!emb_combine_in(c, grp, e)) return;
   const int p = d.p, n = d.n, F = d.F, H = d.H, M1 = d.M1, HC = EMB_HC;
@@ -903,25 +902,25 @@ __device__ __forceinline__ void emb_combine_store(const StepCtx& c, int r, int g
   const int h0 = ch * HC, hc = min(HC, H - h0);
   if (e < ofs_w) {
     const int m = e / HC, hh = e - m * HC;
-    if (hh < hc) rc_store_payload(ws + c.wo.gfc1 + (int64_t)m * p * H + node * H + h0 + hh, t, sc1);
+    if (hh < hc) ws[c.wo.gfc1 + (int64_t)m * p * H + node * H + h0 + hh] = t;
   } else if (e < ofs_s) {
     const int q = e - ofs_w, qh = q >> 4, i = qh / F, f = qh - i * F, hh = q & 15;  // HC == 16
-    if (hh < hc) rc_store_payload(ws + c.wo.dWi + (int64_t)node * n * F * H + ((int64_t)i * F + f) * H + h0 + hh, t, sc1);
+    if (hh < hc) ws[c.wo.dWi + (int64_t)node * n * F * H + ((int64_t)i * F + f) * H + h0 + hh] = t;
   } else if (e < ofs_g) {
-    rc_store_payload(ws + c.wo.dS + (int64_t)grp * n * p + p + (e - ofs_s), t, sc1);
+    ws[c.wo.dS + (int64_t)grp * n * p + p + (e - ofs_s)] = t;
   } else if (e < ofs_h) {
-    rc_store_payload(ws + c.wo.dgb + (int64_t)grp * 2 * F + (e - ofs_g), t, sc1);
+    ws[c.wo.dgb + (int64_t)grp * 2 * F + (e - ofs_g)] = t;
   } else {
-    rc_store_payload(ws + c.wo.gfc + (e - ofs_h), t, sc1);
+    ws[c.wo.gfc + (e - ofs_h)] = t;
   }
 }
 
-__device__ __forceinline__ void emb_combine_elem(const StepCtx& c, int r, int grp, int e, bool sc1) {
-  emb_combine_store(c, r, grp, e, emb_combine_sum(c, r, grp, e), sc1);
+__device__ __forceinline__ void emb_combine_elem(const StepCtx& c, int r, int grp, int e) {
+  emb_combine_store(c, r, grp, e, emb_combine_sum(c, r, grp, e));
 }
 
 __global__ __launch_bounds__(RC_BLOCK) void k_emb_combine(StepCtx c) {
-  emb_combine_elem(c, rc_rep(c, blockIdx.z), blockIdx.y, blockIdx.x * RC_BLOCK + threadIdx.x, false);
+  emb_combine_elem(c, rc_rep(c, blockIdx.z), blockIdx.y, blockIdx.x * RC_BLOCK + threadIdx.x);
 }
 
 // Adjacency-L1 gradient of A summed over the K factors' records, in place into record 0
@@ -1338,15 +1337,29 @@ struct EmbWbSum {
 // register prefetch; small adjacencies get the short code (one-shot code is fetched cold).
 // One workgroup of K4 (wx = 0: the adjacency workgroup, wx >= 1: parameter workgroup wx - 1) of
 // replica slot wy.  fused (c.defer == 2): the parameter workgroups sum the window-block partials
-// in place; sc1: they read the combined records with coherent loads (k_emb_tail, where the
-// combine runs in the same launch); adj_inplace: the adjacency workgroup sums its dS partials in
-// place (k_emb_tail, where it does not wait for the combine).
+// in place; adj_inplace: the adjacency workgroup sums its dS partials in place (k_emb_tail, which
+// runs no combine before it); bn_here: it also updates the BatchNorm running statistics
+// (k_emb_tail gives them a workgroup of their own).
+// BatchNorm running statistics of feature f of replica r from the batch statistics (mean, biased
+// variance) and the current running values (torch: double math, momentum*stat + (1-momentum)*running)
+__device__ __forceinline__ void emb_bn_running(const StepCtx& c, int r, int f, double mean, double var, float rm, float rv) {
+  const double mom = c.hyp[r].bn_momentum;
+  const double N = (double)c.Bg * c.d.p;  // unbiased correction over the global batch
+  const double var_u = var * N / (N - 1.0);
+  for (int t = 0; t < c.nbn; ++t) {
+    rm = (float)(mom * mean + (1.0 - mom) * (double)rm);
+    rv = (float)(mom * var_u + (1.0 - mom) * (double)rv);
+  }
+  c.rm[r * c.d.F + f] = rm;
+  c.rv[r * c.d.F + f] = rv;
+}
+
 #define EF_EPT_MAX 8  // runs per thread of the batched parameter path (k_emb_final's ept <= this)
 #ifndef RC_EF_PMV_FIRST
 #define RC_EF_PMV_FIRST 1  // batched path: parameters / moments requested with (1) or after (0) the gradients
 #endif
 template <int NR>
-__device__ __forceinline__ void emb_final_wg(const StepCtx& c, int wx, int wy, int ept, bool sc1, bool adj_inplace) {
+__device__ __forceinline__ void emb_final_wg(const StepCtx& c, int wx, int wy, int ept, bool adj_inplace, bool bn_here = true) {
   const RedcliffDims& d = c.d;
   const int r = rc_rep(c, wy);
   const int p = d.p, n = d.n, F = d.F, H = d.H, K = d.K, M1 = d.M1;
@@ -1361,14 +1374,13 @@ __device__ __forceinline__ void emb_final_wg(const StepCtx& c, int wx, int wy, i
   // c.defer == 2: the node blocks' window-block partials are summed here (no combine launch);
   // record layout of emb_bwd_node: fc1 chunk | W_i chunk | dS rows i >= 1 | dgamma dbeta | head
   const bool fused = c.defer == 2;
-  auto ldr = [&](const float* q) { return sc1 ? rc_load_sc1(q) : *q; };
   const int HC = EMB_HC, nch = rc_nchunk(d);
   const int ofs_w = M1 * HC, ofs_s = ofs_w + n * F * HC, ofs_g = ofs_s + (n - 1) * p, ofs_h = ofs_g + 2 * F;
   RC_WG_MARK(c.ws, c.wo.total, RC_KID_EMB_FINAL, 0);
   // workgroup 0 is the adjacency workgroup (the longest; dispatched first), 1..nw the parameters
   if (wx > 0) {
     if (!stepA) return;
-    if (!fused && !sc1 && ept > 1 && ept <= EF_EPT_MAX && !(c.flags & RC_GRAD_ONLY)) {
+    if (!fused && ept > 1 && ept <= EF_EPT_MAX && !(c.flags & RC_GRAD_ONLY)) {
       // packed replicas (combined records, several runs per thread): every run's gradient, then
       // the parameters and both moments of all runs requested together and the Adam steps -- one
       // memory round for the workgroup instead of one per run; the same values and operations
@@ -1503,11 +1515,11 @@ __device__ __forceinline__ void emb_final_wg(const StepCtx& c, int wx, int wy, i
       }
     } else if (e < nFH) {
 #pragma unroll 8
-      for (int cc = 0; cc < c.dwN; ++cc) g += ldr(ws + c.wo.dWi + (int64_t)cc * nFH + e);
+      for (int cc = 0; cc < c.dwN; ++cc) g += ws[c.wo.dWi + (int64_t)cc * nFH + e];
       idx = c.eo.gcW + e;
     } else if (e < nFH + nfc) {
       const int q = e - nFH;
-      g = ldr(ws + c.wo.gfc + q);
+      g = ws[c.wo.gfc + q];
       if (q < K * M1) idx = c.eo.fc2W + q;
       else if (q < K * M1 + K) idx = c.eo.fc2b + (q - K * M1);
       else idx = c.eo.fc1b + (q - K * M1 - K);
@@ -1519,13 +1531,13 @@ __device__ __forceinline__ void emb_final_wg(const StepCtx& c, int wx, int wy, i
       int pt = 0;
       for (; pt + 3 < c.dgN; pt += 4)
 #pragma unroll
-        for (int u = 0; u < 4; ++u) g4[u] += ldr(ws + c.wo.dgb + ((int64_t)(pt + u) * 2 + which) * F + f);
-      for (; pt < c.dgN; ++pt) g4[0] += ldr(ws + c.wo.dgb + ((int64_t)pt * 2 + which) * F + f);
+        for (int u = 0; u < 4; ++u) g4[u] += ws[c.wo.dgb + ((int64_t)(pt + u) * 2 + which) * F + f];
+      for (; pt < c.dgN; ++pt) g4[0] += ws[c.wo.dgb + ((int64_t)pt * 2 + which) * F + f];
       g = (g4[0] + g4[1]) + (g4[2] + g4[3]);
       idx = (which == 0 ? c.eo.bnw : c.eo.bnb) + f;
     } else {
       const int q = e - nFH - nfc - 2 * F;  // fc1 weight (gradient combined by the node blocks)
-      g = ldr(ws + c.wo.gfc1 + q);
+      g = ws[c.wo.gfc1 + q];
       idx = c.eo.fc1W + q;
     }
     rc_update(c, E, Mm, V, c.gE + r * c.es, idx, g, as);
@@ -1549,6 +1561,18 @@ __device__ __forceinline__ void emb_final_wg(const StepCtx& c, int wx, int wy, i
   // dense index e of a stack of p x p matrices -> padded LDS index
   auto at = [&](int e) { const int i = dpv.div(e); return i * P + (e - i * p); };
   RC_PHASE(c.ws, c.wo.total, wx, 48);
+  // operands of the BatchNorm running statistics (the workgroup's last phase), requested here so
+  // that their latency is hidden behind the adjacency chain instead of ending the workgroup
+  const bool bn_run = bn_here && c.nbn > 0 && tid < F;
+  double bn_mean = 0.0, bn_var = 0.0;
+  float bn_rm = 0.f, bn_rv = 0.f;
+  if (bn_run) {
+    const double* st = c.bns + r * c.bnsr;
+    bn_mean = st[tid];
+    bn_var = st[F + tid];
+    bn_rm = c.rm[r * F + tid];
+    bn_rv = c.rv[r * F + tid];
+  }
   if (stepA) {
     float* A = E + c.eo.A;
     const float* S = ws + c.wo.S;
@@ -1577,6 +1601,9 @@ __device__ __forceinline__ void emb_final_wg(const StepCtx& c, int wx, int wy, i
           Ar[q] = fmaxf(v, 0.f);
         }),
         rc_seg<NR>((n - 1) * pp2, [&](int e) { return S[pp2 + e]; }, [&](int e, float v) { Sl[PP + at(e)] = v; }),
+        // adjacency-L1 gradient (summed over the factors by k_emb_bwd's reduce workgroups); before
+        // the dS segment, whose sums wait for their loads: every plain load is in flight by then
+        rc_seg<NR>(adjL1 ? pp2 : 0, [&](int e) { return ws[c.wo.dAadj + e]; }, [&](int e, float v) { Sl[at(e)] = v; }),
         // dS_i[c][c'] = fixed-order sum of the backward kernel's partial records
         rc_seg<NR>((n - 1) * pp2, [&](int e) {
           const int i = 1 + e / pp2, rem = e - (i - 1) * pp2, cc = rem / p, cp = rem - cc * p;
@@ -1599,9 +1626,7 @@ __device__ __forceinline__ void emb_final_wg(const StepCtx& c, int wx, int wy, i
             }
           }
           return t;
-        }, [&](int e, float v) { dSw[at(e)] = v; }),
-        // adjacency-L1 gradient (summed over the factors by k_emb_bwd's reduce workgroups)
-        rc_seg<NR>(adjL1 ? pp2 : 0, [&](int e) { return ws[c.wo.dAadj + e]; }, [&](int e, float v) { Sl[at(e)] = v; }));
+        }, [&](int e, float v) { dSw[at(e)] = v; }));
 #ifndef RC_PROBE_NO_BARRIER
     // Every LDS operand above was stored by the thread that loaded it; the row sums below read
     // whole rows, i.e. entries other waves stored.  Without this barrier a wave whose staging
@@ -1679,20 +1704,7 @@ __device__ __forceinline__ void emb_final_wg(const StepCtx& c, int wx, int wy, i
 #endif
   }
   RC_PHASE(c.ws, c.wo.total, wx, 54);
-  // BatchNorm running statistics (torch: double math, momentum*stat + (1-momentum)*running)
-  if (c.nbn > 0 && tid < F) {
-    const double* st = c.bns + r * c.bnsr;
-    const double mom = c.hyp[r].bn_momentum;
-    const double N = (double)c.Bg * p;  // unbiased correction over the global batch
-    const double mean = st[tid], var_u = st[F + tid] * N / (N - 1.0);
-    float rm = c.rm[r * F + tid], rv = c.rv[r * F + tid];
-    for (int t = 0; t < c.nbn; ++t) {
-      rm = (float)(mom * mean + (1.0 - mom) * (double)rm);
-      rv = (float)(mom * var_u + (1.0 - mom) * (double)rv);
-    }
-    c.rm[r * F + tid] = rm;
-    c.rv[r * F + tid] = rv;
-  }
+  if (bn_run) emb_bn_running(c, r, tid, bn_mean, bn_var, bn_rm, bn_rv);
   RC_WG_MARK(c.ws, c.wo.total, RC_KID_EMB_FINAL, 1);
 }
 
@@ -1705,10 +1717,10 @@ __global__ __launch_bounds__(RC_BLOCK) void k_emb_final(StepCtx c, int nw, int e
   // parameter workgroups)
   const int lin = blockIdx.x + blockIdx.y * gridDim.x;
   if (lin < c.nrep) {
-    emb_final_wg<NR>(c, 0, lin, ept, false, false);
+    emb_final_wg<NR>(c, 0, lin, ept, false);
   } else {
     const int wy = (lin - c.nrep) / nw;
-    emb_final_wg<NR>(c, 1 + (lin - c.nrep) - wy * nw, wy, ept, false, false);
+    emb_final_wg<NR>(c, 1 + (lin - c.nrep) - wy * nw, wy, ept, false);
   }
 }
 
@@ -1721,52 +1733,172 @@ __global__ __launch_bounds__(RC_BLOCK) void k_emb_final(StepCtx c, int nw, int e
 template <int NR>
 __global__ __launch_bounds__(RC_BLOCK) void k_emb_final_adj(StepCtx c) {
   rc_critical_priority();
-  emb_final_wg<NR>(c, 0, blockIdx.x, 1, false, false);
+  emb_final_wg<NR>(c, 0, blockIdx.x, 1, false);
 }
 template <int NR>
 __global__ __launch_bounds__(RC_BLOCK) void k_emb_final_params(StepCtx c, int ept) {
   rc_critical_priority();
-  emb_final_wg<NR>(c, 1 + (int)(blockIdx.x & 0xffffff), blockIdx.y, ept, false, false);  // (wx > 0 provably: no adjacency code)
+  emb_final_wg<NR>(c, 1 + (int)(blockIdx.x & 0xffffff), blockIdx.y, ept, false);  // (wx > 0 provably: no adjacency code)
 }
 
-// k_emb_combine + k_emb_final as one launch (single fits with the fused embedder; round 3):
-// workgroup 0 is the adjacency workgroup, which sums its dS partials in place (the sums
-// k_emb_combine forms) and so starts at once; workgroups 1 .. ncomb are the combine's, which
-// store their sums coherently and publish; the parameter workgroups after them wait for all
-// ncomb and then read the combined records coherently.  Producers precede consumers in
-// dispatch order and the whole grid is resident (rc_emb_tail_grid), as in k_bwd_merged; a wait
-// that runs out of polls counts into the status word.  Same sums, same order: the same bits as
-// the two launches (tests/test_gpu_forked.py).  grid (1 + ncomb + nw, R).
-#ifndef TAIL_CE
-#define TAIL_CE 1   // combine elements per thread in k_emb_tail (4: the grid fits C1(K=4) / TST but is slower)
-#endif
-#ifndef TAIL_EPT
-#define TAIL_EPT 1  // parameter elements per thread in k_emb_tail (2: slower, r03_emb_tail_variants.jsonl)
-#endif
+// k_emb_combine + k_emb_final as one launch in which no workgroup waits for another: every
+// parameter workgroup sums the window-block partials of the previous launch in place (plain loads,
+// no counter, no fence), each sum in the order the two launches add it, so the bits are theirs
+// (tests/test_gpu_tail_inplace.py).  Workgroups in dispatch order (rc_tail_roles):
+//   0                the adjacency workgroup (emb_final_wg, dS partials summed in place);
+//   record           one per ((node, chunk) group, RC_BLOCK slice of the record's fc1 part): an fc1
+//                    column belongs to one node, so the window-block sum is the whole gradient;
+//   W_i              ew elements x p nodes: thread (element, node) sums that node's record element
+//                    over the window blocks into LDS, one thread per element adds the p node sums
+//                    in node order (k_emb_final's dwN slices);
+//   BatchNorm affine eb elements x p * nchunk groups into LDS, then the four chains g4[u] (groups
+//                    u, u + 4, ...; the remainder on chain 0) and (g4[0] + g4[1]) + (g4[2] + g4[3]);
+//   head             fc2W | fc2b | fc1b from group 0's record tail;
+//   last             the BatchNorm running statistics (the adjacency workgroup's in k_emb_final).
+// Every thread requests its window-block loads (eight per round) and the parameter and moments it
+// steps before it uses any of them.  No residency condition: any single fit of the fused embedder.
+// grid (1 + record + W_i + BatchNorm + head + 1, R)
+struct TailRoles {
+  int nrx, nrec;  // fc1 slices per group, record workgroups
+  int ew, nwi;    // W_i elements per workgroup, W_i workgroups
+  int eb, nbn;    // BatchNorm-affine elements per workgroup, workgroups
+  int nhd;        // head workgroups
+};
+__host__ __device__ inline TailRoles rc_tail_roles(const RedcliffDims& d) {
+  TailRoles t;
+  const int groups = d.p * rc_nchunk(d);
+  t.nrx = (d.M1 * EMB_HC + RC_BLOCK - 1) / RC_BLOCK;
+  t.nrec = t.nrx * groups;
+  t.ew = RC_BLOCK / d.p;  // (p <= 32: the caller checks p * p <= 4 * RC_BLOCK)
+  t.nwi = (d.n * d.F * d.H + t.ew - 1) / t.ew;
+  t.eb = groups >= RC_BLOCK ? 1 : RC_BLOCK / groups;
+  if (t.eb > 2 * d.F) t.eb = 2 * d.F;
+  t.nbn = (2 * d.F + t.eb - 1) / t.eb;
+  t.nhd = (d.K * d.M1 + d.K + d.M1 + RC_BLOCK - 1) / RC_BLOCK;
+  return t;
+}
+// one record element summed over the window blocks in block order (emb_combine_sum's chain)
+__device__ __forceinline__ float tail_wb_sum(const float* q, int pst, int nbw) {
+  float t = 0.f;
+  for (int w0 = 0; w0 < nbw; w0 += 8) {
+    float v[8];
+#pragma unroll
+    for (int u = 0; u < 8; ++u) v[u] = (w0 + u < nbw) ? q[(int64_t)(w0 + u) * pst] : 0.f;
+#pragma unroll
+    for (int u = 0; u < 8; ++u)
+      if (w0 + u < nbw) t += v[u];
+  }
+  return t;
+}
 template <int NR>
-__global__ __launch_bounds__(RC_BLOCK) void k_emb_tail(StepCtx c, int ncx, int nw) {
+__global__ __launch_bounds__(RC_BLOCK) void k_emb_tail(StepCtx c) {
   rc_critical_priority();
-  const int ncomb = ncx * c.d.p * rc_nchunk(c.d);
-  const int b = blockIdx.x, r = rc_rep(c, blockIdx.y);
-  float* ws = c.ws + r * c.wss;
-  unsigned* cnt = rc_tail_cnt(c, ws);
-  if (b == 0) {
-    emb_final_wg<NR>(c, 0, blockIdx.y, 1, false, true);
+  if (blockIdx.x == 0) {
+    emb_final_wg<NR>(c, 0, blockIdx.y, 1, true, false);
     return;
   }
-  if (b <= ncomb) {
-    const int q = b - 1, grp = q / ncx, x = q - grp * ncx;
-    float t[TAIL_CE];
-#pragma unroll
-    for (int u = 0; u < TAIL_CE; ++u) t[u] = emb_combine_sum(c, r, grp, (x * TAIL_CE + u) * RC_BLOCK + threadIdx.x);
-#pragma unroll
-    for (int u = 0; u < TAIL_CE; ++u) emb_combine_store(c, r, grp, (x * TAIL_CE + u) * RC_BLOCK + threadIdx.x, t[u], true);
-    rc_publish(cnt);
+  if (blockIdx.x == gridDim.x - 1) {  // the BatchNorm running statistics, off the adjacency chain
+    const int r = rc_rep(c, blockIdx.y), f = threadIdx.x;
+    if (c.nbn > 0 && f < c.d.F) {
+      const double* st = c.bns + r * c.bnsr;
+      emb_bn_running(c, r, f, st[f], st[c.d.F + f], c.rm[r * c.d.F + f], c.rv[r * c.d.F + f]);
+    }
     return;
   }
   if (!(c.flags & RC_STEP_A)) return;
-  rc_wait_count(cnt, (unsigned)ncomb, reinterpret_cast<unsigned*>(ws + c.wo.errw), RC_WAIT_POLLS);
-  emb_final_wg<NR>(c, b - ncomb, blockIdx.y, TAIL_EPT, true, false);
+  extern __shared__ float sm[];
+  const RedcliffDims& d = c.d;
+  const int r = rc_rep(c, blockIdx.y), tid = threadIdx.x;
+  const int p = d.p, n = d.n, F = d.F, H = d.H, K = d.K, M1 = d.M1, HC = EMB_HC, nch = rc_nchunk(d);
+  const int ofs_w = M1 * HC, ofs_s = ofs_w + n * F * HC, ofs_g = ofs_s + (n - 1) * p, ofs_h = ofs_g + 2 * F;
+  const int pst = rc_emb_pstride(d), nbw = c.enbw;
+  const int64_t gst = (int64_t)c.enbwm * pst;  // one group's window-block records
+  const float* rec = c.ws + r * c.wss + c.wo.ebp;
+  float* E = c.emb + r * c.es;
+  float* Mm = c.embM + r * c.es;
+  float* V = c.embV + r * c.es;
+  const bool adam = !(c.flags & RC_GRAD_ONLY);
+  const RcAdamScalars as = rc_adam_scalars(c.hyp[r].A, c.tA);
+  const TailRoles tg = rc_tail_roles(d);
+  RC_WG_MARK(c.ws, c.wo.total, RC_KID_EMB_FINAL, 0);
+  int w = blockIdx.x - 1;
+  int64_t idx = -1;            // the parameter this thread steps (-1: none)
+  const float* src = nullptr;  // the record element this thread sums (window block 0; null: none)
+  int role;                    // 0 record, 1 W_i, 2 BatchNorm affine, 3 head (uniform in the workgroup)
+  int el = 0;
+  if (w < tg.nrec) {
+    role = 0;
+    const int grp = w / tg.nrx, e = (w - grp * tg.nrx) * RC_BLOCK + tid;
+    const int node = grp / nch, h0 = (grp - node * nch) * HC, hc = min(HC, H - h0);
+    const int m = e / HC, hh = e - m * HC;
+    if (e < ofs_w && hh < hc) {  // (padding columns of the last chunk carry nothing)
+      src = rec + grp * gst + e;
+      idx = c.eo.fc1W + (int64_t)m * p * H + node * H + h0 + hh;
+    }
+  } else if ((w -= tg.nrec) < tg.nwi) {
+    role = 1;
+    const int node = tid / tg.ew, nFH = n * F * H;
+    el = tid - node * tg.ew;
+    const int e = w * tg.ew + el;  // W_i[i][f][h], ih = i * F + f
+    if (node < p && e < nFH) {
+      const int ih = e / H, h = e - ih * H, ch = h / HC;
+      src = rec + (int64_t)(node * nch + ch) * gst + ofs_w + ih * HC + (h - ch * HC);
+      if (node == 0) idx = c.eo.gcW + e;
+    }
+  } else if ((w -= tg.nwi) < tg.nbn) {
+    role = 2;
+    const int q = w * tg.eb + tid;  // [dgamma | dbeta]
+    if (tid < tg.eb && q < 2 * F) idx = q < F ? c.eo.bnw + q : c.eo.bnb + (q - F);
+  } else if ((w -= tg.nbn) < tg.nhd) {
+    role = 3;
+    const int q = w * RC_BLOCK + tid;  // group 0's record tail: dfc2W | dfc2b | dfc1b
+    if (q < K * M1 + K + M1) {
+      src = rec + ofs_h + q;
+      idx = q < K * M1 ? c.eo.fc2W + q : (q < K * M1 + K ? c.eo.fc2b + (q - K * M1) : c.eo.fc1b + (q - K * M1 - K));
+    }
+  } else {
+    return;
+  }
+  float g;
+  float pv = 0.f, mv = 0.f, vv = 0.f;
+  if (role != 2) {
+    g = src ? tail_wb_sum(src, pst, nbw) : 0.f;
+    if (idx >= 0 && adam) { pv = E[idx]; mv = Mm[idx]; vv = V[idx]; }
+    if (role == 1) {
+      sm[tid] = g;
+      __syncthreads();
+      if (idx >= 0) {
+        g = 0.f;
+        for (int cc = 0; cc < p; ++cc) g += sm[cc * tg.ew + el];
+      }
+    }
+  } else {
+    const int dgN = p * nch, e0 = w * tg.eb;
+    for (int i = tid; i < dgN * tg.eb; i += RC_BLOCK) {
+      const int grp = i / tg.eb, q = e0 + (i - grp * tg.eb);
+      sm[i] = q < 2 * F ? tail_wb_sum(rec + grp * gst + ofs_g + q, pst, nbw) : 0.f;
+    }
+    if (idx >= 0 && adam) { pv = E[idx]; mv = Mm[idx]; vv = V[idx]; }
+    __syncthreads();
+    float g4[4] = {0.f, 0.f, 0.f, 0.f};
+    if (idx >= 0) {
+      int pt = 0;
+      for (; pt + 3 < dgN; pt += 4)
+#pragma unroll
+        for (int u = 0; u < 4; ++u) g4[u] += sm[(pt + u) * tg.eb + tid];
+      for (; pt < dgN; ++pt) g4[0] += sm[pt * tg.eb + tid];
+    }
+    g = (g4[0] + g4[1]) + (g4[2] + g4[3]);
+  }
+  if (idx >= 0) {
+    if (adam) {
+      rc_adam(pv, mv, vv, g, as);
+      E[idx] = pv; Mm[idx] = mv; V[idx] = vv;
+    } else {
+      c.gE[r * c.es + idx] = g;
+    }
+  }
+  RC_WG_MARK(c.ws, c.wo.total, RC_KID_EMB_FINAL, 1);
 }
 
 // BatchNorm batch statistics for consecutive batches: one workgroup per (batch, feature),
@@ -1942,38 +2074,38 @@ static size_t rc_emb_final_lds(const RedcliffDims& d) {
 }
 
 // Workgroups of k_emb_tail per replica, or 0 when the two launches should be used: single fits
-// (R = 1) whose whole grid is resident at the kernel's occupancy (runtime occupancy x CUs).
+// (R = 1) with a small adjacency (the <4> instantiation); no residency condition.
+static size_t rc_emb_tail_lds(const RedcliffDims& d) {
+  const size_t adj = rc_emb_final_lds(d), groups = (size_t)d.p * rc_nchunk(d);
+  const size_t stage = sizeof(float) * (groups > RC_BLOCK ? groups : RC_BLOCK);  // W_i / BatchNorm staging
+  return adj > stage ? adj : stage;
+}
 int rc_emb_tail_grid(const StepCtx& c) {
   const RedcliffDims& d = c.d;
-  if (c.nrep != 1 || d.p * d.p > 4 * RC_BLOCK) return 0;
-  const int total = d.n * d.F * d.H + d.K * d.M1 + d.K + d.M1 + 2 * d.F + d.M1 * d.p * d.H;
-  const int nw = (total + TAIL_EPT * RC_BLOCK - 1) / (TAIL_EPT * RC_BLOCK);
-  const int ncx = (rc_emb_pstride(d) + TAIL_CE * RC_BLOCK - 1) / (TAIL_CE * RC_BLOCK);
-  const int grid = 1 + ncx * d.p * rc_nchunk(d) + nw;
-  const size_t lds = rc_emb_final_lds(d);
-  static thread_local size_t cached_lds = (size_t)-1;
-  static thread_local int occ = 0;
-  if (lds != cached_lds) {
-    occ = 0;
-    if (rc_lds_optin(k_emb_tail<4>, lds, "k_emb_tail LDS") != 0 ||
-        hipOccupancyMaxActiveBlocksPerMultiprocessor(&occ, k_emb_tail<4>, RC_BLOCK, lds) != hipSuccess)
-      occ = 0;
-    cached_lds = lds;
-  }
-  return grid <= occ * rc_cu_count() ? grid : 0;
+  if (c.nrep != 1 || d.p * d.p > 4 * RC_BLOCK || rc_emb_tail_lds(d) > RC_LDS_MAX_FLOATS * sizeof(float)) return 0;
+  const TailRoles t = rc_tail_roles(d);
+  return 1 + t.nrec + t.nwi + t.nbn + t.nhd + 1;
+}
+
+// Dependent memory rounds of the tail's adjacency workgroup while it sums its dS partials in place
+// (emb_final_wg's staging: NR * RC_BLOCK elements per pass, EmbWbSum::nodes: four groups x eight
+// window blocks in flight per element).  The workgroup is the tail's longest, and each round adds
+// about 2.5 us to it, while the combine launch the tail saves is worth about 5 us: measured
+// 1 round (D4IC) 0.0562 -> 0.0524 ms per step, 2 rounds (C1(K=4)) 0.0781 -> 0.0746,
+// 4 rounds (TST) 0.0916 -> 0.0926, so the step takes the tail up to 2 rounds.
+int rc_emb_tail_adj_rounds(const StepCtx& c) {
+  const RedcliffDims& d = c.d;
+  const int elems = (d.n - 1) * d.p * d.p;
+  return ((elems + RC_BLOCK - 1) / RC_BLOCK) * ((rc_nchunk(d) + 3) / 4) * ((c.enbw + 7) / 8);
 }
 
 int rc_launch_emb_tail(const StepCtx& c, hipStream_t s) {
-  const RedcliffDims& d = c.d;
   const int grid = rc_emb_tail_grid(c);
-  if (grid == 0 || c.defer != 1) { rc_set_error("embedder tail launch: grid not resident or defer != 1"); return REDCLIFF_EINVAL; }
-  const int total = d.n * d.F * d.H + d.K * d.M1 + d.K + d.M1 + 2 * d.F + d.M1 * d.p * d.H;
-  const int nw = (total + TAIL_EPT * RC_BLOCK - 1) / (TAIL_EPT * RC_BLOCK);
-  const int ncx = (rc_emb_pstride(d) + TAIL_CE * RC_BLOCK - 1) / (TAIL_CE * RC_BLOCK);
-  const size_t lds = rc_emb_final_lds(d);
+  if (grid == 0 || c.defer != 1) { rc_set_error("embedder tail launch: not a single fit or defer != 1"); return REDCLIFF_EINVAL; }
+  const size_t lds = rc_emb_tail_lds(c.d);
   int e = rc_lds_optin(k_emb_tail<4>, lds, "k_emb_tail LDS");
   if (e) return e;
-  hipLaunchKernelGGL(k_emb_tail<4>, dim3(grid, c.nrep), dim3(RC_BLOCK), lds, s, c, ncx, nw);
+  hipLaunchKernelGGL(k_emb_tail<4>, dim3(grid, c.nrep), dim3(RC_BLOCK), lds, s, c);
   return rc_check(hipGetLastError(), "k_emb_tail");
 }
 

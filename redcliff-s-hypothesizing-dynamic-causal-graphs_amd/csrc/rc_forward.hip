@@ -275,7 +275,7 @@ __device__ __attribute__((always_inline)) void emb_fwd_body(const StepCtx& c, in
   fc1(std::integral_constant<int, NBT>{});  // NBT >= SB (k_forward's instantiation for this launch)
   if (zs >= 0) {  // arrival: the last of the window's Zs workgroups sums the partials and runs fc2
     __shared__ unsigned last;
-    unsigned* cnt = reinterpret_cast<unsigned*>(ws + c.wo.ecnt) + p * rc_nchunk(d) + 2 + b0;
+    unsigned* cnt = reinterpret_cast<unsigned*>(ws + c.wo.ecnt) + p * rc_nchunk(d) + 1 + b0;
     asm volatile("s_waitcnt vmcnt(0)" ::: "memory");  // every storing wave drains its partials
     __syncthreads();
     if (tid == 0) last = __hip_atomic_fetch_add(cnt, 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) == (unsigned)(Zs - 1);
@@ -423,11 +423,8 @@ __global__ __launch_bounds__(RC_BLOCK) void k_forward(StepCtx c, int SB, int w_l
   extern __shared__ float sm[];
   // every step with an embedder forward re-arms the merged backward's factor-lead counter (the
   // kernel boundary orders this store before k_bwd_merged's polls)
-  if (blockIdx.x == 0 && nemb > 0 && threadIdx.x == 0) {  // the counters of this step's later launches
-    unsigned* lc = rc_fac_lead_cnt(c, c.ws + rc_rep(c, blockIdx.y) * c.wss);
-    lc[0] = 0u;  // merged backward: published factor leads
-    lc[1] = 0u;  // k_emb_tail: published combine workgroups
-  }
+  if (blockIdx.x == 0 && nemb > 0 && threadIdx.x == 0)
+    *rc_fac_lead_cnt(c, c.ws + rc_rep(c, blockIdx.y) * c.wss) = 0u;  // published factor leads
   if ((int)blockIdx.x < nemb) {
     if (split) {
       const RcDiv32 dZs = cs == (int)c.mg[RC_MG_CS] ? RcDiv32(c.fzs, c.mg[RC_MG_ZS]) : RcDiv32((c.d.p + cs - 1) / cs);

@@ -20,6 +20,8 @@ def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--config", default="d4ic")
     ap.add_argument("--steps", type=int, default=5)
+    ap.add_argument("--final-roles", default=None,
+                    help="name:count,... (count * = the rest): per-role start / end times of the embedder tail's workgroups")
     args = ap.parse_args()
     from redcliff_amd import build as b
     from redcliff_amd import _native
@@ -77,6 +79,20 @@ def main():
                  (st.max() - st.min()) / 100.0, dur.min(), np.median(dur), dur.max()))
 
 
+    if args.final_roles:  # e.g. adj:1,combine:160,params:* -- workgroup ranges of the emb_final slots
+        st, en = tr[4][0::2], tr[4][1::2]
+        t0 = int(st[st > 0].min())
+        lo = 0
+        for part in args.final_roles.split(","):
+            name, cnt = part.split(":")
+            hi = 1024 if cnt == "*" else lo + int(cnt)
+            ok = (st[lo:hi] > 0) & (en[lo:hi] > 0)
+            if ok.any():
+                s_, e_ = st[lo:hi][ok], en[lo:hi][ok]
+                print("emb_final role %-8s WGs %4d  first start %6.2f us  last start %6.2f  first end %6.2f  last end %6.2f"
+                      % (name, ok.sum(), (s_.min() - t0) / 100.0, (s_.max() - t0) / 100.0, (e_.min() - t0) / 100.0,
+                         (e_.max() - t0) / 100.0))
+            lo = hi
     pub = tr[7][1::2]
     pub = pub[pub > 0]
     if pub.size:
