@@ -494,6 +494,62 @@ typedef struct RedcliffFMArgs {
 int redcliff_fm_supported(const RedcliffDims* d);
 int redcliff_fm_run(const RedcliffFMArgs* a, void* stream);
 
+/* ---- the cLSTM forecasting baseline cLSTM_FM (models/clstm_fm.py:56-177, 341-393) ----
+ * Purely additive entries: REDCLIFF_ABI_VERSION stays 10, no kernel id, no existing entry or layout
+ * changes.
+ *
+ * The model is one cLSTM (models/clstm.py: p networks nn.LSTM(p, h) -> Conv1d(h, 1, 1)) with no
+ * embedder; its loss is c_forecast * sum_i MSE(pred[:, :, i], target[:, :, i]) + c_adj * sum_j sum_c
+ * ||weight_ih_j[:, c]||_2, one Adam.  The loss separates over the p networks, so one launch on grid
+ * (p, stepped replicas) runs nsteps = ceil(N / B) consecutive batch_updates (:141-177) of the
+ * recordings X[row0 + i*B ...] (the last batch may be ragged): workgroup (j, r) keeps network j's
+ * weights and Adam moments in LDS for the whole call and writes them back once.
+ * With C = context, S = tmax - C sequences per recording, Bq = B_i * S, sequence (n, s) reads rows
+ * s .. s+C of recording n in place (arrange_input, :95-112, is never materialised).  Per step i:
+ *   t = 0..C-1:  a = Wih x[n][s+t] + Whh h_{t-1} + (bih + bhh)   (gate rows i | f | g | o, h_{-1} = c_{-1} = 0)
+ *                c_t = sig(a_f) c_{t-1} + sig(a_i) tanh(a_g)     h_t = sig(a_o) tanh(c_t)
+ *                y_t = Wl . h_t + bl                             res = y_t - x[n][s+t+1][j]
+ *   dy = c_forecast * 2 / (Bq * C) * res                          (RC_LOSS_FORECAST)
+ *   backward through time into dWih, dWhh, dbih = dbhh, dWl, dbl
+ *   dWih[:, c] += c_adj * Wih[:, c] / G[c], G[c] = ||Wih[:, c]||_2  (RC_LOSS_ADJ; 0 where G[c] == 0)
+ *   Adam of hyper[r].B at step number tB + i on each of the six tensors   (RC_STEP_B)
+ * Packed layout of a replica's block (fac, fac_m, fac_v alike), each torch parameter a contiguous view:
+ *   Wih[p][4h][p] | Whh[p][4h][h] | bih[p][4h] | bhh[p][4h] | Wl[p][h] | bl[p]
+ * Outputs: sse[i'][i][j] = sum res^2 over the batch's Bq * C residuals and, with RC_VALUES,
+ * pen[i'][i][j] = sum_c G[c] at the weights step i used (i' = the i'-th stepped replica in ascending
+ * order); when G is given, G[r][j][c] of the final weights (indexed by replica).
+ * Without RC_STEP_B the call is the batch body of training_sim_eval (:341-393): the parameters are
+ * only read, the moments are not touched (fac_m / fac_v may be NULL).
+ * X[N][T][p] is device-resident; only rows [0, tmax) of a recording are read.  Replica r reads
+ * X + r*x_pstride (0: all replicas fit the same set) and its block at fac + r*fac_stride.
+ * Limits: p <= 64, h <= 64, context <= 64, Bmax <= 512, R <= 256 and
+ *   4*(4h*Kp + 9h + 1) + 32*(((C+1)K | 1) + (4hC | 1) + (hC | 1) + 2(h | 1) + 2C) + p + 16 <= 40960
+ * floats of LDS (K = p + h, Kp = K | 1), which binds first: h <= 35 at p = 4, C = 2; h <= 33 at p = 10,
+ * C = 2; h <= 18 at p = 64, C = 2; p <= 35 at h = 25, C = 2; context <= 34 at p = 4, h = 5; context <= 4
+ * at p = 10, h = 25.  Outside them REDCLIFF_ELIMIT.  Null buffers, flags outside the four above,
+ * B < 1 or > Bmax, N < 0, tmax <= context, tmax > T, a bad active list, negative strides:
+ * REDCLIFF_EINVAL.  N == 0 or an empty list launches nothing.  All checks precede any HIP call.
+ * Stream-ordered, no atomics, every sum in an order fixed by (p, h, context, tmax) and the batch size:
+ * a replica's bits do not depend on R, the active list, or on how [row0, row0 + N) is split into
+ * calls at multiples of B. */
+typedef struct RedcliffLstmFMArgs {
+  RedcliffDims d;            /* R, Bmax, T, p, h read; every other field is ignored                   */
+  int32_t context, tmax;     /* sequence length C; rows [0, tmax) of a recording are used             */
+  int32_t flags;             /* RC_LOSS_FORECAST | RC_LOSS_ADJ | RC_STEP_B | RC_VALUES                */
+  int32_t B, tB;             /* recordings per batch; Adam step number of the first step (1-based)    */
+  int64_t row0, N;           /* recordings [row0, row0 + N) in batches of B                           */
+  const float* X; int64_t x_pstride;
+  float* fac; float* fac_m; float* fac_v; int64_t fac_stride;
+  const RedcliffReplicaHyper* hyper;        /* device [R]: c_forecast, c_adj, B (Adam) read            */
+  float* sse; float* pen;    /* [n stepped][nsteps][p]; pen may be NULL without RC_VALUES              */
+  float* G;                  /* optional final norms [R][p][p], may be NULL                            */
+  const int32_t* replicas; int32_t n_replicas;   /* as RedcliffStepArgs.replicas                      */
+} RedcliffLstmFMArgs;
+/* Host-only limit query: 0 outside the limits (with a redcliff_last_error message), else the
+ * workgroup's LDS footprint in floats. */
+int redcliff_lstm_fm_supported(const RedcliffDims* d, int32_t context);
+int redcliff_lstm_fm_run(const RedcliffLstmFMArgs* a, void* stream);
+
 /* Per-kernel HIP-event timing for benchmarking: redcliff_kernel_timing(1) brackets every
  * kernel launched by redcliff_train_step with events on its stream; redcliff_kernel_times()
  * synchronises them and returns per-kernel totals (ids 0..11: supports, emb_fwd, fac_fwd,

@@ -38,6 +38,34 @@ def factor_layout(K, p, h, L):
     return o
 
 
+def lstm_layout(p, h):
+    """Offsets (floats) of one cLSTM's packed parameters Wih[p][4h][p] | Whh[p][4h][h] | bih[p][4h] |
+    bhh[p][4h] | Wl[p][h] | bl[p] (redcliff_lstm_fm_run)."""
+    o = {"Wih": 0}
+    o["Whh"] = o["Wih"] + p * 4 * h * p
+    o["bih"] = o["Whh"] + p * 4 * h * h
+    o["bhh"] = o["bih"] + p * 4 * h
+    o["Wl"] = o["bhh"] + p * 4 * h
+    o["bl"] = o["Wl"] + p * h
+    o["total"] = o["bl"] + p
+    return o
+
+
+def lstm_views(flat, clstm, p, h):
+    """(param, view) pairs mapping each parameter of a cLSTM, in parameters() order, onto lstm_layout."""
+    o = lstm_layout(p, h)
+    g = 4 * h
+    pairs = []
+    for j, net in enumerate(clstm.networks):
+        pairs.append((net.lstm.weight_ih_l0, flat[o["Wih"] + j * g * p:o["Wih"] + (j + 1) * g * p].view(g, p)))
+        pairs.append((net.lstm.weight_hh_l0, flat[o["Whh"] + j * g * h:o["Whh"] + (j + 1) * g * h].view(g, h)))
+        pairs.append((net.lstm.bias_ih_l0, flat[o["bih"] + j * g:o["bih"] + (j + 1) * g]))
+        pairs.append((net.lstm.bias_hh_l0, flat[o["bhh"] + j * g:o["bhh"] + (j + 1) * g]))
+        pairs.append((net.linear.weight, flat[o["Wl"] + j * h:o["Wl"] + (j + 1) * h].view(1, h, 1)))
+        pairs.append((net.linear.bias, flat[o["bl"] + j:o["bl"] + j + 1]))
+    return pairs
+
+
 def factor_views(flat, cmlps, p, h, L):
     """(param, view) pairs mapping each cMLP parameter onto the packed factor layout
     W0[K][p][h][p][L] | b0[K][p][h] | W1[K][p][h] | b1[K][p]."""
