@@ -550,6 +550,62 @@ typedef struct RedcliffLstmFMArgs {
 int redcliff_lstm_fm_supported(const RedcliffDims* d, int32_t context);
 int redcliff_lstm_fm_run(const RedcliffLstmFMArgs* a, void* stream);
 
+/* ---- the NAVAR (MLP) additive baseline (models/navar.py:9-125) ----
+ * Purely additive entries: REDCLIFF_ABI_VERSION stays 10, no kernel id, no existing entry or layout
+ * changes.
+ *
+ * N per-source networks (K lags of series i -> H units -> (H units) -> N contributions) whose
+ * contributions are summed into one prediction before the loss, so the networks are NOT independent.
+ * RedcliffDims carries the shape: p = N (nodes), h = H (num_hidden), L = K (maxlags), n = hidden
+ * layers (1 or 2), Bmax, T >= K + 1 (rows [0, K) of a window are the lags, row K the target), R.
+ * Packed layout of a replica's block (par, par_m, par_v alike), each torch parameter a contiguous view:
+ *   W1[N][H][K] | b1[N][H] | (W2[N][H][H] | b2[N][H] with two layers) | Wc[N][N][H] | bc[N][N] | biases[N]
+ * Arithmetic of one step over the Bi windows X[perm[q]], q in [s*B, s*B + Bi):
+ *   z1 = W1_i x_i + b1_i, h1 = max(z1, 0); (z2 = W2_i h1 + b2_i, h2 = max(z2, 0)); c_ij = Wc_i[j] . h + bc_ij
+ *   pred_j = sum_i c_ij (i ascending) + biases_j;  res = pred - y;  mse = sum res^2 / (Bi N)
+ *   dc_ij = 2 res_j / (Bi N) + lambda1 / (N Bi) sign(c_ij) (sign(0) = 0); clamp passes the gradient where z >= 0
+ *   Adam of hyper[r].B at step number tB + s (coupled weight decay); lambda1 = hyper[r].c_adj
+ * REDCLIFF_NAVAR_TRAIN: nsteps = ceil(N / B) steps, three launches each on the one stream (forward
+ * partials per (unit slice, source), backward + update of the last layer / contributions, update of the
+ * first layer and biases); launch boundaries are the only cross-workgroup dependencies, no atomics, no
+ * grid barrier.  Outputs mse[i'][s] and l1[i'][s] = (lambda1 / N) mean_b sum_ij |c_ij| (i' = the i'-th
+ * stepped replica in ascending order).  perm values are clamped into [0, nX).
+ * REDCLIFF_NAVAR_FORWARD: rows [row0, row0 + N) of X in order -> pred[i'][N][N nodes],
+ * contrib[i'][N][N*N] (channel i*N + j); parameters are only read, par_m / par_v / hyper / perm unused.
+ * Replica r reads X + r*x_pstride (0: shared), perm + r*perm_pstride (0: shared), its block at
+ * par + r*par_stride.  ws: n_stepped * (N*nS*B*N + [two] N*nS*B*H + 32) floats, nS = ceil(H / 32);
+ * shorter gives REDCLIFF_EWORKSPACE.
+ * Limits: N <= 32, H <= 512, K <= 64, Bmax <= 512, R <= 256, layers 1 or 2, T >= K + 1 and
+ *   64*(K|1) + 4224 + 66*N + 128*(N|1) + 240 + (two ? 128*(ceil16(H)|1) : 32*(K|1)) <= 40960 floats of LDS
+ * (two layers: H <= 256 at N = 10, K = 20); outside them REDCLIFF_ELIMIT (the query returns 0).  Null
+ * buffers, a bad mode, B < 1 or > Bmax, N < 0, row0 + N > nX in FORWARD, a bad active list, negative
+ * strides: REDCLIFF_EINVAL.  N == 0 or an empty list launches nothing.  All checks precede any HIP
+ * call.  Every sum's order is fixed by the shape and the batch size: a replica's bits do not depend on
+ * R, the active list, or on how the steps are split into calls at multiples of B. */
+#define REDCLIFF_NAVAR_TRAIN 0
+#define REDCLIFF_NAVAR_FORWARD 1
+typedef struct RedcliffNavarArgs {
+  RedcliffDims d;            /* R, Bmax, T, p = N, h = H, L = K, n = hidden layers read               */
+  int32_t mode;              /* REDCLIFF_NAVAR_TRAIN | REDCLIFF_NAVAR_FORWARD                         */
+  int32_t B, tB;             /* batch size; Adam step number of the first step (1-based)              */
+  int32_t launches;          /* TRAIN, for profiling: 0 = all three launches of a step, else a mask of      */
+                             /* 1 = k_navar_fwd, 2 = k_navar_bwd, 4 = k_navar_in (the others are skipped)    */
+  int64_t row0, N;           /* FORWARD: rows [row0, row0 + N); TRAIN: perm[0 .. N), row0 ignored      */
+  int64_t nX;                /* rows of one window set                                                */
+  const float* X; int64_t x_pstride;
+  const int32_t* perm; int64_t perm_pstride;
+  float* par; float* par_m; float* par_v; int64_t par_stride;
+  const RedcliffReplicaHyper* hyper;        /* device [R]: c_adj = lambda1, B (Adam) read             */
+  float* mse; float* l1;     /* TRAIN: [n stepped][nsteps]                                            */
+  float* pred; float* contrib;              /* FORWARD: [n stepped][N][N nodes] / [n stepped][N][N*N]  */
+  float* ws; size_t ws_bytes;
+  const int32_t* replicas; int32_t n_replicas;   /* as RedcliffStepArgs.replicas                     */
+} RedcliffNavarArgs;
+/* Host-only limit query: 0 outside the limits (with a redcliff_last_error message), else the
+ * workgroup's LDS footprint in floats. */
+int redcliff_navar_supported(const RedcliffDims* d);
+int redcliff_navar_run(const RedcliffNavarArgs* a, void* stream);
+
 /* Per-kernel HIP-event timing for benchmarking: redcliff_kernel_timing(1) brackets every
  * kernel launched by redcliff_train_step with events on its stream; redcliff_kernel_times()
  * synchronises them and returns per-kernel totals (ids 0..11: supports, emb_fwd, fac_fwd,

@@ -14,8 +14,10 @@ from .scoring import score_recordings
 from .cmlp_fm import cMLP_FM, fit_baselines
 from .clstm import LSTM, cLSTM
 from .clstm_fm import cLSTM_FM, fit_lstm_baselines
+from .navar import NAVAR, fit_navar_baselines
 
 __all__ = ["MLP", "cMLP", "DGCNN", "DGCNN_Model", "DGCNN_Embedder", "cEmbedder", "MLPClassifierForSingleObjective",
            "MLPClassifierForMultipleObjectives", "REDCLIFF_S_CMLP", "REDCLIFF_S_CMLP_withStateSmoothing", "ReplicaPack",
            "PerReplica", "fit_packs", "grid_packs", "shard_grid", "DataParallelFit",
-           "score_recordings", "cMLP_FM", "fit_baselines", "LSTM", "cLSTM", "cLSTM_FM", "fit_lstm_baselines"]
+           "score_recordings", "cMLP_FM", "fit_baselines", "LSTM", "cLSTM", "cLSTM_FM", "fit_lstm_baselines",
+           "NAVAR", "fit_navar_baselines"]

@@ -44,7 +44,8 @@ EXPORTED = ("redcliff_abi_version", "redcliff_last_error", "redcliff_workspace_b
             "redcliff_score_recording_workspace_bytes", "redcliff_score_recording",
             "redcliff_cemb_score_supported", "redcliff_cemb_score_recording",
             "redcliff_score_recording_pack_workspace_bytes", "redcliff_score_recording_pack",
-            "redcliff_fm_supported", "redcliff_fm_run", "redcliff_lstm_fm_supported", "redcliff_lstm_fm_run")
+            "redcliff_fm_supported", "redcliff_fm_run", "redcliff_lstm_fm_supported", "redcliff_lstm_fm_run",
+            "redcliff_navar_supported", "redcliff_navar_run")
 CEMB_WS_REGIONS = ("ha", "w1", "g", "g0", "E", "E0", "dE", "draw")
 KERNEL_IDS = ("supports", "emb_fwd", "fac_fwd", "fac_bwd", "emb_bwd", "emb_final", "fac_mix", "emb_combine", "fac_lead",
               "score", "score_graphs", "score_cemb")
@@ -136,6 +137,15 @@ class LstmFMArgs(ctypes.Structure):
                 ("sse", _vp), ("pen", _vp), ("G", _vp), ("replicas", _vp), ("n_replicas", ctypes.c_int32)]
 
 
+class NavarArgs(ctypes.Structure):
+    """RedcliffNavarArgs (redcliff_navar_run)."""
+    _fields_ = [("d", Dims), ("mode", ctypes.c_int32), ("B", ctypes.c_int32), ("tB", ctypes.c_int32),
+                ("launches", ctypes.c_int32), ("row0", _i64), ("N", _i64), ("nX", _i64), ("X", _vp), ("x_pstride", _i64),
+                ("perm", _vp), ("perm_pstride", _i64), ("par", _vp), ("par_m", _vp), ("par_v", _vp), ("par_stride", _i64),
+                ("hyper", _vp), ("mse", _vp), ("l1", _vp), ("pred", _vp), ("contrib", _vp),
+                ("ws", _vp), ("ws_bytes", ctypes.c_size_t), ("replicas", _vp), ("n_replicas", ctypes.c_int32)]
+
+
 def adam_hyper(lr, betas, eps, weight_decay):
     b1, b2 = float(betas[0]), float(betas[1])
     return AdamHyper(float(lr), b1, b2, float(eps), float(weight_decay), b2, 1.0 - b1, 1.0 - b2, 0)
@@ -208,6 +218,8 @@ def lib():
     L.redcliff_fm_run.argtypes = [ctypes.POINTER(FMArgs), _vp]
     L.redcliff_lstm_fm_supported.argtypes = [ctypes.POINTER(Dims), ctypes.c_int32]
     L.redcliff_lstm_fm_run.argtypes = [ctypes.POINTER(LstmFMArgs), _vp]
+    L.redcliff_navar_supported.argtypes = [ctypes.POINTER(Dims)]
+    L.redcliff_navar_run.argtypes = [ctypes.POINTER(NavarArgs), _vp]
     for name in EXPORTED[2:]:
         if name not in ("redcliff_workspace_bytes", "redcliff_emb_param_count", "redcliff_fac_param_count",
                         "redcliff_build_id", "redcliff_cemb_param_count", "redcliff_cemb_workspace_bytes",
