@@ -606,6 +606,65 @@ typedef struct RedcliffNavarArgs {
 int redcliff_navar_supported(const RedcliffDims* d);
 int redcliff_navar_run(const RedcliffNavarArgs* a, void* stream);
 
+/* ---- the NAVAR (LSTM) additive baseline (models/navar.py:129-246, model type "NAVAR_CLSTM") ----
+ * Purely additive entries: REDCLIFF_ABI_VERSION stays 10, no kernel id, no existing entry or layout
+ * changes.
+ *
+ * N per-source one-layer LSTMs (input size 1, H units) over the T' = T - 1 first rows of a window, each
+ * followed by a Linear(H, N) applied at every time step; the N x N contributions are summed over the
+ * sources into one prediction per time step.  RedcliffDims carries p = N, h = H, T = window rows
+ * (T' = T - 1 LSTM steps, row T' the target), Bmax and R; the other fields are not read.
+ * Packed layout of a replica's block (par, par_m, par_v alike), each torch parameter a contiguous view,
+ * gate order i, f, g, o:
+ *   Wih[N][4H] | Whh[N][4H][H] | bih[N][4H] | bhh[N][4H] | Wfc[N][N][H] | bfc[N][N] | biases[N]
+ * Arithmetic of one step over the Bi windows X[perm[q]], q in [s*B, s*B + Bi):
+ *   pre_t = Whh_i h_{t-1} (k ascending, fp32 matrix cores) + (Wih_i x_t + (bih_i + bhh_i)), h_{-1} = c_{-1} = 0
+ *   c_t = f c_{t-1} + i g, h_t = o tanh(c_t);  con_ij(t) = Wfc_i[j] . h_t (units ascending, from bfc_ij)
+ *   pred_j(t) = sum_i con_ij(t) (i ascending) + biases_j;  res_j = pred_j(T'-1) - X[row][T'][j]
+ *   mse = sum res^2 / (Bi N);  l1 = (lambda1 / N) sum_{t,b,ij} |con| / (Bi T')
+ *   dcon_ij(t) = [t = T'-1] 2 res_j / (Bi N) + lambda1 / (N Bi T') sign(con_ij(t)) (sign(0) = 0); with
+ *   lambda1 == 0 only t = T'-1 is formed (the other terms are exact zeros)
+ *   Adam of hyper[r].B at step number tB + s (coupled weight decay); lambda1 = hyper[r].c_adj
+ * REDCLIFF_NAVAR_TRAIN: nsteps = ceil(N / B) steps of 2T' + 5 launches each on the one stream: T' forward
+ * launches over (16-unit slice, source, replica), the output layer, the loss / small-gradient
+ * reduction, T' backward launches (t descending, same grid), the dWhh product (one GEMM per source,
+ * k = (t, b) ascending) and the element-wise Adam.  Launch boundaries are the only cross-workgroup
+ * dependencies: no atomics, no grid barrier, no workgroup waits on another.  Outputs mse[i'][s] and
+ * l1[i'][s] (i' = the i'-th stepped replica in ascending order).  perm values are clamped into [0, nX).
+ * REDCLIFF_NAVAR_FORWARD: rows [row0, row0 + N) of X in order -> pred[i'][N][N nodes][T'],
+ * contrib[i'][N * T'][N*N] (row b*T' + t, channel i*N + j); parameters are only read.
+ * ws: n_stepped * rc_navar_lstm_ws floats (redcliff_navar_lstm_ws_floats); shorter gives
+ * REDCLIFF_EWORKSPACE.
+ * Limits: N <= 32, H <= 448, T' in [1, 64], Bmax <= 512, R <= 256 and
+ *   64*(ceil16(H)|1) + 64*65 + 64*(N|1) + 64*17 + 34*N + 384 <= 40960 floats of LDS
+ * (true everywhere inside the other limits); outside them REDCLIFF_ELIMIT (the query returns 0).
+ * Argument errors as redcliff_navar_run.  All checks precede any HIP call.  Every sum's order is fixed by
+ * (N, H, T', batch size): a replica's bits do not depend on R, the active list, or on how the steps are
+ * split into calls at multiples of B. */
+typedef struct RedcliffNavarLstmArgs {
+  RedcliffDims d;            /* R, Bmax, T, p = N, h = H read                                         */
+  int32_t mode;              /* REDCLIFF_NAVAR_TRAIN | REDCLIFF_NAVAR_FORWARD                         */
+  int32_t B, tB;             /* batch size; Adam step number of the first step (1-based)              */
+  int32_t launches;          /* TRAIN, for profiling: 0 = all launches of a step, else a mask of       */
+                             /* 1 = forward, 2 = output + reduction, 4 = backward, 8 = dWhh + Adam     */
+  int64_t row0, N;           /* FORWARD: rows [row0, row0 + N); TRAIN: perm[0 .. N), row0 ignored      */
+  int64_t nX;                /* rows of one window set                                                */
+  const float* X; int64_t x_pstride;
+  const int32_t* perm; int64_t perm_pstride;
+  float* par; float* par_m; float* par_v; int64_t par_stride;
+  const RedcliffReplicaHyper* hyper;        /* device [R]: c_adj = lambda1, B (Adam) read             */
+  float* mse; float* l1;     /* TRAIN: [n stepped][nsteps]                                            */
+  float* pred; float* contrib;              /* FORWARD: [n stepped][N][N nodes][T'] / [..][N*T'][N*N]  */
+  float* ws; size_t ws_bytes;
+  const int32_t* replicas; int32_t n_replicas;   /* as RedcliffStepArgs.replicas                     */
+} RedcliffNavarLstmArgs;
+/* Host-only limit query: 0 outside the limits (with a redcliff_last_error message), else the
+ * backward workgroup's LDS footprint in floats. */
+int redcliff_navar_lstm_supported(const RedcliffDims* d);
+/* Workspace floats of one stepped replica at batch size B (train: 1 = TRAIN, 0 = FORWARD). */
+int64_t redcliff_navar_lstm_ws_floats(const RedcliffDims* d, int32_t B, int32_t train);
+int redcliff_navar_lstm_run(const RedcliffNavarLstmArgs* a, void* stream);
+
 /* Per-kernel HIP-event timing for benchmarking: redcliff_kernel_timing(1) brackets every
  * kernel launched by redcliff_train_step with events on its stream; redcliff_kernel_times()
  * synchronises them and returns per-kernel totals (ids 0..11: supports, emb_fwd, fac_fwd,

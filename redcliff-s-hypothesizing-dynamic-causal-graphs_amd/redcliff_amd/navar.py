@@ -17,7 +17,7 @@ Two routes, chosen by ``REDCLIFF_NAVAR_PATH=fused|generic`` (default fused):
 
 ``fit_navar_baselines`` fits R same-shape models (e.g. the 15 fold fits of
 train/NAVAR_CMLP_d4IC_BCTVgs1Parsim.py) with the replica on a grid axis; ``NAVAR.fit`` is that function
-with lists of one.  NAVARLSTM (models/navar.py:129-246) is not provided.
+with lists of one.  NAVARLSTM (models/navar.py:129-246) is redcliff_amd.navar_lstm.
 """
 import ctypes
 import os
