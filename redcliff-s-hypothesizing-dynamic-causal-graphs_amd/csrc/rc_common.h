@@ -587,6 +587,41 @@ typedef float f32x16 __attribute__((ext_vector_type(16)));
 typedef float f32x4 __attribute__((ext_vector_type(4)));
 __device__ inline int mf_row(int reg, int lane) { return (reg & 3) + 8 * (reg >> 2) + 4 * (lane >> 5); }
 
+// A v_mfma_f32_16x16x4_f32 chain over the contraction index [0, n), NB k-steps per batch: the
+// 2 NB operands of a batch are read before its first MFMA, so the batch costs one LDS round
+// trip instead of one per step.  la / lb(kc) read lane group lg's operand of index k = k0 + lg
+// unconditionally at the clamped index kc = min(k, n - 1) (CLAMP = false: at k itself, for tiles
+// whose padding up to the batch is addressable); pa / pb(k) say whether the operand exists, and a zero is selected where it does not (a guarded read is a branch and a wait per
+// step; a product with a stale word could be NaN).  The scheduling barrier keeps the compiler
+// from sinking the reads back between the products.  Same steps in the same order as the
+// one-step loop: k-steps at k0 >= n are skipped whole (wave-uniform), never replaced by zero
+// products.
+template <int NB, bool CLAMP, class LA, class LB, class PA, class PB>
+__device__ __forceinline__ f32x4 rc_mfma_chain16(f32x4 acc, int n, int lg, LA la, LB lb, PA pa, PB pb) {
+  for (int k0 = 0; k0 < n; k0 += 4 * NB) {
+    float av[NB], bv[NB];
+#pragma unroll
+    for (int s = 0; s < NB; ++s) {
+      const int k = k0 + 4 * s + lg, kc = CLAMP ? min(k, n - 1) : k;
+      av[s] = la(kc);
+      bv[s] = lb(kc);
+    }
+    __builtin_amdgcn_sched_barrier(0);
+#pragma unroll
+    for (int s = 0; s < NB; ++s) {
+      const int k = k0 + 4 * s + lg;
+      if (k0 + 4 * s >= n) break;
+      acc = __builtin_amdgcn_mfma_f32_16x16x4f32(pa(k) ? av[s] : 0.f, pb(k) ? bv[s] : 0.f, acc, 0, 0, 0);
+    }
+  }
+  return acc;
+}
+template <int NB, bool CLAMP, class LA, class LB>
+__device__ __forceinline__ f32x4 rc_mfma_chain16(f32x4 acc, int n, int lg, LA la, LB lb) {
+  auto in = [n](int k) { return k < n; };
+  return rc_mfma_chain16<NB, CLAMP>(acc, n, lg, la, lb, in, in);
+}
+
 // Block-wide sum; every thread gets the result.  `red` must hold >= RC_BLOCK/64 floats.
 __device__ inline float rc_block_sum(float v, float* red) {
   v = rc_wave_sum(v);

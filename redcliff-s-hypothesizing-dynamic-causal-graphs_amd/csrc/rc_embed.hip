@@ -293,6 +293,9 @@ __device__ __forceinline__ void emb_bwd_head(const StepCtx& c, int r, float* sm)
 // place (2), or by the block that arrives last (0: agent-scope release / ticket / acquire,
 // cdna_hip_programming.md §6 Guideline 16).  The first sub-block's inputs and the
 // fixed operands are staged by one multi-segment pass (one memory latency for everything).
+#ifndef EMB_KB
+#define EMB_KB 4  // k-steps per operand batch of the df1 / dZ matrix-core chains (rc_mfma_chain16)
+#endif
 template <bool MULTI, bool LATE = false>
 __device__ __forceinline__ void emb_bwd_node(const StepCtx& c, int r, int node, int ch, int wb, int BC, int WPB, float* sm,
                              const unsigned* wait_cnt = nullptr, unsigned wait_target = 0) {
@@ -525,48 +528,51 @@ __device__ __forceinline__ void emb_bwd_node(const StepCtx& c, int r, int node, 
       __syncthreads();
       // df1[s][m] = [f1 > 0] sum_k dr[s][k] fc2W[k][m]: wave w, columns m in [16 w, 16 w + 16)
       if (16 * wv < M1) {
-        const int m = 16 * wv + l15;
-        f32x4 a = {0.f, 0.f, 0.f, 0.f};
-        for (int k0 = 0; k0 < K; k0 += 4) {
-          const int k = k0 + lg;
-          const float av = k < K ? dr[l15 * K + k] : 0.f;
-          const float bv = (k < K && m < M1) ? fc2s[k * M1 + m] : 0.f;
-          a = __builtin_amdgcn_mfma_f32_16x16x4f32(av, bv, a, 0, 0, 0);
-        }
+        // (operands fetched ahead of their chains, rc_mfma_chain16: unconditional reads at clamped
+        // indices, zeros selected afterwards; the epilogue's f1 operands are read before the chain)
+        const int m = 16 * wv + l15, mc = min(m, M1 - 1);
+        float f1v[4];
+#pragma unroll
+        for (int reg = 0; reg < 4; ++reg) f1v[reg] = f1r[(4 * lg + reg) * M1 + mc];
+        const f32x4 a = rc_mfma_chain16<EMB_KB, true>(
+            f32x4{0.f, 0.f, 0.f, 0.f}, K, lg,
+            [&](int kc) { return dr[l15 * K + kc]; }, [&](int kc) { return fc2s[kc * M1 + mc]; },
+            [&](int k) { return k < K; }, [&](int k) { return k < K && m < M1; });
         if (m < M1)
 #pragma unroll
           for (int reg = 0; reg < 4; ++reg) {
             const int sw = 4 * lg + reg;
-            df1c[sw * M1 + m] = (sw < nbc && f1r[sw * M1 + m] > 0.f) ? a[reg] : 0.f;
+            df1c[sw * M1 + m] = (sw < nbc && f1v[reg] > 0.f) ? a[reg] : 0.f;
           }
       }
       __syncthreads();
   RC_PHASE(c.ws, c.wo.total, pbx, 35);
       // dZ[s][hh] = [R > 0] sum_m df1[s][m] fc1W[m][hh]: wave 0
       if (wv == 0) {
-        f32x4 a = {0.f, 0.f, 0.f, 0.f};
-        for (int m0 = 0; m0 < M1; m0 += 4) {
-          const int m = m0 + lg;
-          const float av = m < M1 ? df1c[l15 * M1 + m] : 0.f;
-          const float bv = m < M1 ? FW[m * HC + l15] : 0.f;
-          a = __builtin_amdgcn_mfma_f32_16x16x4f32(av, bv, a, 0, 0, 0);
-        }
+        float rv[4];
 #pragma unroll
-        for (int reg = 0; reg < 4; ++reg) {
-          const int e = (4 * lg + reg) * HC + l15;
-          dZc[e] = Rc[e] > 0.f ? a[reg] : 0.f;
-        }
+        for (int reg = 0; reg < 4; ++reg) rv[reg] = Rc[(4 * lg + reg) * HC + l15];
+        const f32x4 a = rc_mfma_chain16<EMB_KB, true>(
+            f32x4{0.f, 0.f, 0.f, 0.f}, M1, lg,
+            [&](int mc) { return df1c[l15 * M1 + mc]; }, [&](int mc) { return FW[mc * HC + l15]; });
+#pragma unroll
+        for (int reg = 0; reg < 4; ++reg) dZc[(4 * lg + reg) * HC + l15] = rv[reg] > 0.f ? a[reg] : 0.f;
       }
       // dfc1W chunk partial: afc[m][hh] += sum_s df1[s][m] R[s][hh]: wave w, rows m in [16 w, 16 w + 16)
       if (16 * wv < M1) {
-        const int m = 16 * wv + l15;
+        const int m = 16 * wv + l15, mc = min(m, M1 - 1);
         f32x4 accA = {afc[0], afc[1], afc[2], afc[3]};
+        float av[4], bv[4];
 #pragma unroll
-        for (int s0 = 0; s0 < 16; s0 += 4) {
-          const int sw = s0 + lg;
-          const float av = m < M1 ? df1c[sw * M1 + m] : 0.f;
-          accA = __builtin_amdgcn_mfma_f32_16x16x4f32(av, Rc[sw * HC + l15], accA, 0, 0, 0);
+        for (int s4 = 0; s4 < 4; ++s4) {
+          const int sw = 4 * s4 + lg;
+          av[s4] = df1c[sw * M1 + mc];
+          bv[s4] = Rc[sw * HC + l15];
         }
+        __builtin_amdgcn_sched_barrier(0);
+#pragma unroll
+        for (int s4 = 0; s4 < 4; ++s4)
+          accA = __builtin_amdgcn_mfma_f32_16x16x4f32(m < M1 ? av[s4] : 0.f, bv[s4], accA, 0, 0, 0);
 #pragma unroll
         for (int reg = 0; reg < 4; ++reg) afc[reg] = accA[reg];
       }
@@ -598,23 +604,28 @@ __device__ __forceinline__ void emb_bwd_node(const StepCtx& c, int r, int node, 
       for (int i = 0; i < 4; ++i) {
         const int qt = wv + 4 * i;
         if (16 * qt >= nF) break;
-        const int q = 16 * qt + l15;
+        const int q = 16 * qt + l15, qc = min(q, nF - 1);
         f32x4 accW = {awi[4 * i], awi[4 * i + 1], awi[4 * i + 2], awi[4 * i + 3]};
+        // the 16 operands of the tile's two chains are read before the first product
+        float tv[4], zv[4], zt[4], wvl[4];
 #pragma unroll
-        for (int s0 = 0; s0 < 16; s0 += 4) {
-          const int sw = s0 + lg;
-          const float av = q < nF ? Tc[sw * nF + q] : 0.f;
-          accW = __builtin_amdgcn_mfma_f32_16x16x4f32(av, dZc[sw * HC + l15], accW, 0, 0, 0);
+        for (int s4 = 0; s4 < 4; ++s4) {
+          const int sw = 4 * s4 + lg;  // (window of dW_i's step s4; hidden unit of dT's)
+          tv[s4] = Tc[sw * nF + qc];
+          wvl[s4] = WiC[qc * HP + sw];
+          zv[s4] = dZc[sw * HC + l15];
+          zt[s4] = dZc[l15 * HC + sw];
         }
+        __builtin_amdgcn_sched_barrier(0);
+#pragma unroll
+        for (int s4 = 0; s4 < 4; ++s4)
+          accW = __builtin_amdgcn_mfma_f32_16x16x4f32(q < nF ? tv[s4] : 0.f, zv[s4], accW, 0, 0, 0);
 #pragma unroll
         for (int reg = 0; reg < 4; ++reg) awi[4 * i + reg] = accW[reg];
         f32x4 a = {0.f, 0.f, 0.f, 0.f};
 #pragma unroll
-        for (int hq = 0; hq < 16; hq += 4) {
-          const int hh = hq + lg;
-          const float bv = q < nF ? WiC[q * HP + hh] : 0.f;
-          a = __builtin_amdgcn_mfma_f32_16x16x4f32(dZc[l15 * HC + hh], bv, a, 0, 0, 0);
-        }
+        for (int s4 = 0; s4 < 4; ++s4)
+          a = __builtin_amdgcn_mfma_f32_16x16x4f32(zt[s4], q < nF ? wvl[s4] : 0.f, a, 0, 0, 0);
         if (q < nF)
 #pragma unroll
           for (int reg = 0; reg < 4; ++reg) dTc[(4 * lg + reg) * nF + q] = a[reg];

@@ -16,6 +16,11 @@ namespace {
 #ifndef RC_FB_MFMA
 #define RC_FB_MFMA 1  // activation recompute and dW0 tile on v_mfma_f32_16x16x4_f32 (same chains)
 #endif
+#ifndef FB_KB
+#define FB_KB 4  // k-steps per operand batch of those chains (rc_mfma_chain16; 4 measured best)
+#endif
+// (a batch's reads past Q or nb stay inside the tiles' rows: no index clamp in these chains)
+static_assert(FB_QT % (4 * FB_KB) == 0 && FB_BT % (4 * FB_KB) == 0, "operand batches must tile the LDS tiles");
 
 template <class Div>
 __device__ inline float xwin(const StepCtx& c, const Div& dL, const float* X, int b, int q) {
@@ -123,7 +128,8 @@ __device__ __forceinline__ void fac_bwd_wg(const StepCtx& c, int nUl, int nQ, in
   auto tile_u = [&](int jj) { return RC_FB_MFMA ? 4 * flg + jj : (tid >> 4); };
   auto tile_q = [&](int jj) { return RC_FB_MFMA ? 16 * fwv + fl15 : (tid & 15) + 16 * jj; };
   const int tq = tid & 15, tu = tid >> 4;
-  const int64_t kjW0 = c.fo.W0 + (int64_t)kj * h * Q;
+  // (32-bit offsets inside the replica's factor slice: K p h p L <= 2^29 floats at the engine's limits)
+  const int kjW0 = (int)c.fo.W0 + kj * h * Q;
   float pw[4] = {0.f, 0.f, 0.f, 0.f}, pm[4] = {0.f, 0.f, 0.f, 0.f}, pv[4] = {0.f, 0.f, 0.f, 0.f};
   float sb[6] = {0.f, 0.f, 0.f, 0.f, 0.f, 0.f}, s1[3] = {0.f, 0.f, 0.f};
   const bool gonly = c.flags & RC_GRAD_ONLY;
@@ -134,17 +140,17 @@ __device__ __forceinline__ void fac_bwd_wg(const StepCtx& c, int nUl, int nQ, in
       for (int jj = 0; jj < 4; ++jj) {
         const int u = u0 + tile_u(jj), q = q0 + tile_q(jj);
         if (u < h && q < Q) {
-          const int64_t idx = kjW0 + (int64_t)u * Q + q;
+          const int idx = kjW0 + u * Q + q;
           pw[jj] = P[idx]; pm[jj] = PM[idx]; pv[jj] = PV[idx];
         }
       }
       if (qc == 0 && tid < FAC_UC && u0 + tid < h) {
-        const int64_t ib = c.fo.b0 + (int64_t)kj * h + u0 + tid, iw = c.fo.W1 + (int64_t)kj * h + u0 + tid;
+        const int ib = (int)c.fo.b0 + kj * h + u0 + tid, iw = (int)c.fo.W1 + kj * h + u0 + tid;
         sb[0] = P[ib]; sb[1] = PM[ib]; sb[2] = PV[ib];
         sb[3] = P[iw]; sb[4] = PM[iw]; sb[5] = PV[iw];
       }
       if (qc == 0 && uc == 0 && tid == 0) {
-        const int64_t i1 = c.fo.b1 + kj;
+        const int i1 = (int)c.fo.b1 + kj;
         s1[0] = P[i1]; s1[1] = PM[i1]; s1[2] = PV[i1];
       }
     }
@@ -165,10 +171,10 @@ __device__ __forceinline__ void fac_bwd_wg(const StepCtx& c, int nUl, int nQ, in
         }, [&](int e, float v) { awl[(e >> 4) * (FAC_UC + 1) + (e & 15)] = v; }),
         rc_seg<4>(on && stepB && recompute ? FAC_UC * Q : 0, [&](int e) {
           const int uu = e / Q, q = e - uu * Q;
-          return u0 + uu < h ? P[kjW0 + (int64_t)(u0 + uu) * Q + q] : 0.f;
+          return u0 + uu < h ? P[kjW0 + (u0 + uu) * Q + q] : 0.f;
         }, [&](int e, float v) { Wc[(e / Q) * (FB_QT + 1) + e % Q] = v; }),
         rc_seg<1>(on && stepB && recompute ? FAC_UC : 0, [&](int e) {
-          return u0 + e < h ? P[c.fo.b0 + (int64_t)kj * h + u0 + e] : 0.f;
+          return u0 + e < h ? P[(int)c.fo.b0 + kj * h + u0 + e] : 0.f;
         }, [&](int e, float v) { bc0[e] = v; }),
         rc_seg<32>(on && stepB ? nb0 * FB_QT : 0, [&](int e) {
           const int bb = e >> 6, qq = e & 63;
@@ -367,19 +373,17 @@ __device__ __forceinline__ void fac_bwd_wg(const StepCtx& c, int nUl, int nQ, in
     // k-ascending fmaf chain per output from 0: the forward's chain, so the same bits; the
     // columns q >= Q of the last k step are zeros (exact no-ops).  Wave w: window tiles w, w + 4.
     for (int bt = fwv; bt < (nb + 15) / 16; bt += 4) {
-      f32x4 z = {0.f, 0.f, 0.f, 0.f};
       const float* xr = Xs + (16 * bt + fl15) * (FB_QT + 1);
       const float* wr = Wc + fl15 * (FB_QT + 1);
-      for (int k0 = 0; k0 < Q; k0 += 4) {
-        const int k = k0 + flg;
-        const float av = k < Q ? xr[k] : 0.f, bv = k < Q ? wr[k] : 0.f;
-        z = __builtin_amdgcn_mfma_f32_16x16x4f32(av, bv, z, 0, 0, 0);
-      }
+      const float b0v = bc0[fl15];  // (read ahead of the chain: the epilogue's four stores need no wait)
+      const f32x4 z = rc_mfma_chain16<FB_KB, false>(
+          f32x4{0.f, 0.f, 0.f, 0.f}, Q, flg,
+          [&](int kc) { return xr[kc]; }, [&](int kc) { return wr[kc]; });
       const bool uin = u0 + fl15 < h;
 #pragma unroll
       for (int reg = 0; reg < 4; ++reg) {
         const int b = 16 * bt + 4 * flg + reg;
-        if (b < nb) awl[b * (FAC_UC + 1) + fl15] = uin ? fmaxf(z[reg] + bc0[fl15], 0.f) : 0.f;
+        if (b < nb) awl[b * (FAC_UC + 1) + fl15] = uin ? fmaxf(z[reg] + b0v, 0.f) : 0.f;
       }
     }
     __syncthreads();
@@ -459,12 +463,9 @@ __device__ __forceinline__ void fac_bwd_wg(const StepCtx& c, int nUl, int nQ, in
       // tile_q's
       f32x4 a4 = {acc[0], acc[1], acc[2], acc[3]};
       const float* xc = Xs + 16 * fwv + fl15;
-      for (int k0 = 0; k0 < nb; k0 += 4) {
-        const int b = k0 + flg;
-        const float av = b < nb ? awl[b * (FAC_UC + 1) + fl15] : 0.f;
-        const float bv = b < nb ? xc[b * (FB_QT + 1)] : 0.f;
-        a4 = __builtin_amdgcn_mfma_f32_16x16x4f32(av, bv, a4, 0, 0, 0);
-      }
+      const float* zc = awl + fl15;
+      a4 = rc_mfma_chain16<FB_KB, false>(
+          a4, nb, flg, [&](int bc) { return zc[bc * (FAC_UC + 1)]; }, [&](int bc) { return xc[bc * (FB_QT + 1)]; });
 #pragma unroll
       for (int jj = 0; jj < 4; ++jj) acc[jj] = a4[jj];
     } else {
@@ -488,10 +489,10 @@ __device__ __forceinline__ void fac_bwd_wg(const StepCtx& c, int nUl, int nQ, in
         g1 += rA[s2 * 16 + tid];
         g0 += rB[s2 * 16 + tid];
       }
-      rc_adam_pre(c, P, PM, PV, GF, c.fo.b0 + (int64_t)kj * h + u0 + tid, g0, as, sb[0], sb[1], sb[2]);
-      rc_adam_pre(c, P, PM, PV, GF, c.fo.W1 + (int64_t)kj * h + u0 + tid, g1, as, sb[3], sb[4], sb[5]);
+      rc_adam_pre(c, P, PM, PV, GF, (int)c.fo.b0 + kj * h + u0 + tid, g0, as, sb[0], sb[1], sb[2]);
+      rc_adam_pre(c, P, PM, PV, GF, (int)c.fo.W1 + kj * h + u0 + tid, g1, as, sb[3], sb[4], sb[5]);
     }
-    if (uc == 0 && tid == 0) rc_adam_pre(c, P, PM, PV, GF, c.fo.b1 + kj, db1, as, s1[0], s1[1], s1[2]);
+    if (uc == 0 && tid == 0) rc_adam_pre(c, P, PM, PV, GF, (int)c.fo.b1 + kj, db1, as, s1[0], s1[1], s1[2]);
   }
   RC_PHASE(c.ws, c.wo.total, tbx, 22);
   // dW0 tile: + adjacency-L1 term through the group norms, then Adam
@@ -500,7 +501,7 @@ __device__ __forceinline__ void fac_bwd_wg(const StepCtx& c, int nUl, int nQ, in
     for (int jj = 0; jj < 4; ++jj) {
       const int u = u0 + tile_u(jj), q = q0 + tile_q(jj);
       if (u >= h || q >= Q) continue;
-      const int64_t idx = kjW0 + (int64_t)u * Q + q;
+      const int idx = kjW0 + u * Q + q;
       float g = acc[jj];
       if (adj_grad && Gs[q] > 0.f) g += dGs[q] * ((gonly ? P[idx] : pw[jj]) / Gs[q]);
       rc_adam_pre(c, P, PM, PV, GF, idx, g, as, pw[jj], pm[jj], pv[jj]);
