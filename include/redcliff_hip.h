@@ -665,6 +665,70 @@ int redcliff_navar_lstm_supported(const RedcliffDims* d);
 int64_t redcliff_navar_lstm_ws_floats(const RedcliffDims* d, int32_t B, int32_t train);
 int redcliff_navar_lstm_run(const RedcliffNavarLstmArgs* a, void* stream);
 
+/* ---- the supervised DGCNN baseline as a stand-alone fit (models/dgcnn.py:63-237, model type "DGCNN") ----
+ * Purely additive entries: REDCLIFF_ABI_VERSION stays 10, no kernel id, no existing entry or layout
+ * changes.
+ *
+ * RedcliffDims carries the shape: p = nodes n, F = features per node, n = Chebyshev layers, H = hidden
+ * channels, K = classes C, Bmax, T >= F (rows [0, F) of a window X[row][T][n] are the features), R; M1 is
+ * taken as 64.  Packed layout of a replica's block (par, par_m, par_v alike), the embedder's, each torch
+ * parameter a contiguous view:
+ *   A[n][n] | gcW[layers][F][H] | bn_w[F] | bn_b[F] | fc1W[64][n*H] | fc1b[64] | fc2W[C][64] | fc2b[C]
+ * bn_rm / bn_rv: [R][F] running statistics.  Y: [nX][C] labels, already selected.
+ * Arithmetic of one step over the Bi rows [row0 + s*B, row0 + s*B + Bi):
+ *   x_b[k][f] = X[row][f][k];  BatchNorm over the Bi*n values of feature f (batch statistics in double, the
+ *   biased variance normalises, the unbiased one goes to the running variance with hyper[r].bn_momentum)
+ *   L = (dinv_i relu(A)_ik) dinv_k, dinv_i = 1 / sqrt(sum_k relu(A)_ik + 1e-10);  S_0 = I, S_1 = L, S_i = S_{i-1} L
+ *   Z_b = sum_i (S_i x_b) W_i (supports ascending), R = relu(Z), f1 = fc1 flat(R) (nodes ascending) + fc1b,
+ *   out = fc2 relu(f1) + fc2b, loss = sum (out - y)^2 / (Bi C);  ReLU passes no gradient at 0
+ *   Adam of hyper[r].B at step number tB + s (coupled weight decay) on every parameter; with one layer A has
+ *   no gradient and is left untouched together with its moments (torch's Adam skips a parameter without one)
+ * REDCLIFF_DGCNN_FIT_TRAIN: one statistics launch for the call, then nsteps = ceil(N / B) steps of three
+ * launches each on the one stream (per-node forward partials; head + per-node backward + Adam on the node's
+ * fc1 block; the sums over nodes, dA and Adam on the rest, running statistics).  Launch boundaries are the
+ * only cross-workgroup dependencies: no atomics, no grid barrier, no workgroup waits on another.  Output
+ * loss[i'][s] (i' = the i'-th stepped replica in ascending order).  num_batches_tracked is the caller's.
+ * REDCLIFF_DGCNN_FIT_FORWARD: eval mode (running statistics) over rows [row0, row0 + N) in batches of B ->
+ * pred[i'][N][C] and, when Y is given, loss[i'][s] = the MSE of batch s; parameters are only read, par_m /
+ * par_v unused.
+ * Replica r reads X + r*x_pstride (0: shared), Y + r*y_pstride (0: shared), its block at par + r*par_stride.
+ * ws: n_stepped * redcliff_dgcnn_fit_ws_floats(d, B, N) floats, 8-byte aligned; shorter gives
+ * REDCLIFF_EWORKSPACE.
+ * Limits: nodes <= 32, F <= 8, layers <= 4, hid <= 256, classes <= 16, Bmax <= 128, R <= 256, T >= F and
+ *   max(256 + Bmax*(65 + C) + 64*C + 96*(hid|1) + 32*F*n + 96*layers*F + n*n + layers*n + layers*F*(hid|1),
+ *       256 + (2*layers + 3)*n*n) <= 40960 floats of LDS
+ * outside them REDCLIFF_ELIMIT (the queries return 0).  Null buffers, a bad mode, B < 1 or > Bmax, N < 0,
+ * row0 < 0, row0 + N > nX, a bad active list, negative strides: REDCLIFF_EINVAL.  N == 0 or an empty list
+ * launches nothing.  All checks precede any HIP call.  Every sum's order is fixed by the shape and the
+ * batch size: a replica's bits do not depend on R, the active list, on whether data is shared, or on how the
+ * steps are split into calls at multiples of B. */
+#define REDCLIFF_DGCNN_FIT_TRAIN 0
+#define REDCLIFF_DGCNN_FIT_FORWARD 1
+typedef struct RedcliffDgcnnFitArgs {
+  RedcliffDims d;            /* R, Bmax, T, p = nodes, F, n = layers, H = hid, K = classes read          */
+  int32_t mode;              /* REDCLIFF_DGCNN_FIT_TRAIN | REDCLIFF_DGCNN_FIT_FORWARD                    */
+  int32_t B, tB;             /* batch size; Adam step number of the first step (1-based)                 */
+  int32_t launches;          /* TRAIN, for profiling: 0 = all three launches of a step, else a mask of    */
+                             /* 1 = k_dg_fwd, 2 = k_dg_bwd, 4 = k_dg_tail (the others are skipped)        */
+  int64_t row0, N;           /* rows [row0, row0 + N) of X / Y                                           */
+  int64_t nX;                /* rows of one window set                                                   */
+  const float* X; int64_t x_pstride;
+  const float* Y; int64_t y_pstride;        /* FORWARD: may be NULL (no loss)                            */
+  float* par; float* par_m; float* par_v; int64_t par_stride;
+  float* bn_rm; float* bn_rv;               /* [R][F]                                                    */
+  const RedcliffReplicaHyper* hyper;        /* device [R]: bn_eps, bn_momentum, B (Adam) read            */
+  float* loss;               /* [n stepped][nsteps]                                                      */
+  float* pred;               /* FORWARD: [n stepped][N][C]                                               */
+  float* ws; size_t ws_bytes;
+  const int32_t* replicas; int32_t n_replicas;   /* as RedcliffStepArgs.replicas                        */
+} RedcliffDgcnnFitArgs;
+/* Host-only limit query: 0 outside the limits (with a redcliff_last_error message), else the
+ * workgroup's LDS footprint in floats. */
+int redcliff_dgcnn_fit_supported(const RedcliffDims* d);
+/* Workspace floats of one stepped replica for a call over N rows at batch size B (0: outside the limits). */
+int64_t redcliff_dgcnn_fit_ws_floats(const RedcliffDims* d, int32_t B, int64_t N);
+int redcliff_dgcnn_fit_run(const RedcliffDgcnnFitArgs* a, void* stream);
+
 /* Per-kernel HIP-event timing for benchmarking: redcliff_kernel_timing(1) brackets every
  * kernel launched by redcliff_train_step with events on its stream; redcliff_kernel_times()
  * synchronises them and returns per-kernel totals (ids 0..11: supports, emb_fwd, fac_fwd,

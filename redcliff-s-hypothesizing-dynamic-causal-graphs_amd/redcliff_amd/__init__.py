@@ -3,7 +3,7 @@
 Drop-in classes for the reference's models/ modules; compute in libredcliff_hip.so
 (gfx950 HIP kernels, C-ABI in include/redcliff_hip.h)."""
 from .cmlp import MLP, cMLP
-from .dgcnn import DGCNN, DGCNN_Model
+from .dgcnn import DGCNN, DGCNN_Model, fit_dgcnn_baselines
 from .redcliff_factor_score_embedders import (DGCNN_Embedder, MLPClassifierForMultipleObjectives,
                                               MLPClassifierForSingleObjective, cEmbedder)
 from .redcliff_s_cmlp import REDCLIFF_S_CMLP
@@ -21,4 +21,4 @@ __all__ = ["MLP", "cMLP", "DGCNN", "DGCNN_Model", "DGCNN_Embedder", "cEmbedder",
            "MLPClassifierForMultipleObjectives", "REDCLIFF_S_CMLP", "REDCLIFF_S_CMLP_withStateSmoothing", "ReplicaPack",
            "PerReplica", "fit_packs", "grid_packs", "shard_grid", "DataParallelFit",
            "score_recordings", "cMLP_FM", "fit_baselines", "LSTM", "cLSTM", "cLSTM_FM", "fit_lstm_baselines",
-           "NAVAR", "fit_navar_baselines", "NAVARLSTM", "fit_navar_lstm_baselines"]
+           "NAVAR", "fit_navar_baselines", "NAVARLSTM", "fit_navar_lstm_baselines", "fit_dgcnn_baselines"]
