@@ -369,7 +369,8 @@ inline int rc_rep_host(const StepCtx& c, int i) { return rc_rep(c, i); }
 #define RC_KID_EMB_BWD 3
 #define RC_KID_EMB_FINAL 4
 #define RC_KID_FAC_MIX 5
-#define RC_KID_EMB_WAIT 7  // merged backward: a node workgroup's hand-off wait returned (start slot only)
+#define RC_KID_EMB_WAIT 7  // merged backward: start slot = a node workgroup's hand-off wait returned, or (the K*p
+                           // lead workgroups' slots) a lead's stage-1 publish; end slot = a lead's stage-2 publish
 #ifdef RC_TRACE
 #define RC_WG_MARK(wsbase, total, kid, end)                                                        \
   do {                                                                                            \
@@ -423,19 +424,25 @@ __device__ inline void rc_store_payload(float* p, float v, bool sc1) {
     *p = v;
 }
 
-__device__ inline void rc_publish(unsigned* cnt) {
+// The factor leads publish in two stages on ONE counter word: stage 1 ("the dL/dw partials are in
+// memory", all a node workgroup reads) counts in the low half, stage 2 ("every record is in
+// memory", what the dA-reduce workgroups read) in the high half; a waiter compares its half with
+// K*p (<= 16 * 64, far below 2^16).  One word, so k_forward's re-arm store clears both.
+#define RC_PUB_DWP 0u   // shift of the stage-1 count
+#define RC_PUB_ALL 16u  // shift of the stage-2 count
+__device__ inline void rc_publish(unsigned* cnt, unsigned shift) {
   asm volatile("s_waitcnt vmcnt(0)" ::: "memory");  // every storing wave drains its sc1 stores
   __syncthreads();
-  if (threadIdx.x == 0) __hip_atomic_fetch_add(cnt, 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+  if (threadIdx.x == 0) __hip_atomic_fetch_add(cnt, 1u << shift, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
 }
 
 #define RC_WAIT_POLLS (1u << 24)      // ~1 s of s_sleep(2) polls
 #define RC_WAIT_POLLS_DBG (1u << 12)  // the forced-timeout debug mode
 
-__device__ inline void rc_wait_count(const unsigned* cnt, unsigned target, unsigned* status, unsigned polls) {
+__device__ inline void rc_wait_count(const unsigned* cnt, unsigned shift, unsigned target, unsigned* status, unsigned polls) {
   if (threadIdx.x == 0) {
     unsigned spins = 0;
-    while (__hip_atomic_load(const_cast<unsigned*>(cnt), __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) < target) {
+    while (((__hip_atomic_load(const_cast<unsigned*>(cnt), __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) >> shift) & 0xffffu) < target) {
       if (++spins >= polls) {
         __hip_atomic_fetch_add(status, 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
         break;
@@ -451,9 +458,10 @@ __device__ inline void rc_wait_count(const unsigned* cnt, unsigned target, unsig
 __device__ inline unsigned* rc_fac_lead_cnt(const StepCtx& c, float* ws) {
   return reinterpret_cast<unsigned*>(ws + c.wo.ecnt) + c.d.p * ((c.d.H + EMB_HC - 1) / EMB_HC);
 }
-// a consumer of the merged backward waits for `target` published factor leads of replica slice ws
-__device__ inline void rc_wait_leads(const StepCtx& c, float* ws, const unsigned* cnt, unsigned target) {
-  rc_wait_count(cnt, target + (c.wait_dbg ? 1u : 0u), reinterpret_cast<unsigned*>(ws + c.wo.errw),
+// a consumer of the merged backward waits for `target` factor leads of replica slice ws to have
+// published stage `shift` (RC_PUB_DWP / RC_PUB_ALL)
+__device__ inline void rc_wait_leads(const StepCtx& c, float* ws, const unsigned* cnt, unsigned shift, unsigned target) {
+  rc_wait_count(cnt, shift, target + (c.wait_dbg ? 1u : 0u), reinterpret_cast<unsigned*>(ws + c.wo.errw),
                 c.wait_dbg ? RC_WAIT_POLLS_DBG : RC_WAIT_POLLS);
 }
 

@@ -498,7 +498,7 @@ __device__ __forceinline__ void emb_bwd_node(const StepCtx& c, int r, int node, 
 #endif
       if (!MULTI && tid < F) bn_affine_store(c, r, tid, bnq, alpha, beta, mean, inv);
       if (wait_now) {
-        rc_wait_leads(c, c.ws + r * c.wss, wait_cnt, wait_target);
+        rc_wait_leads(c, c.ws + r * c.wss, wait_cnt, RC_PUB_DWP, wait_target);  // dwp is all a node reads
         RC_WG_MARK(c.ws, c.wo.total, RC_KID_EMB_WAIT, 0);
         dw_load(0);
       }
@@ -1003,14 +1003,18 @@ void k_emb_bwd(StepCtx c, int nnode, int head, int BC, int WPB) {
 // adjacency-L1 dL/dA records, which the K*p factor-lead workgroups (mixing, forecast residual,
 // adjacency L1) write early; the rest of the factor backward (dW0 / Adam) is independent of
 // it.  Workgroup order: [K*p factor leads][embedder node / head / dA-reduce workgroups][the
-// other factor workgroups]; node and reduce workgroups wait on the leads' published count
-// (rc_wait_count), everything else runs free.  Same arithmetic in the same order as the two
-// launches, so the results are bit-identical (tests/test_gpu_replicas.py).
+// other factor workgroups]; node workgroups wait on the leads' stage-1 count (dL/dw in memory),
+// reduce workgroups on the stage-2 count (rc_wait_count), everything else runs free.  Same
+// arithmetic in the same order as the two launches, so the results are bit-identical
+// (tests/test_gpu_replicas.py, tests/test_gpu_chain_edges.py, tests/test_gpu_publish_stages.py).
 // RC_MERGED_WAVES (experiment builds): a floor of waves per SIMD for the single-sub-block merged
 // kernel (0: the compiler's choice, 217 VGPRs + 24 AGPRs = 2 waves; 3 caps it at 168 registers with
 // 116 bytes of scratch per lane, and 3 workgroups per CU make C1(K=4)'s 681-workgroup grid resident)
 #ifndef RC_MERGED_WAVES
 #define RC_MERGED_WAVES 0
+#endif
+#ifndef RC_MERGED_FAC_PRIO
+#define RC_MERGED_FAC_PRIO 3  // s_setprio of the factor workgroups' waves in k_bwd_merged<false> (0: none)
 #endif
 template <bool MULTI>
 __global__ __launch_bounds__(RC_BLOCK) __attribute__((amdgpu_waves_per_eu(MULTI || RC_MERGED_WAVES == 0 ? 1 : RC_MERGED_WAVES)))
@@ -1026,7 +1030,7 @@ void k_bwd_merged(StepCtx c, int nUl, int nQ, int nnode, int head, int nred,
   if (e >= 0 && e < nemb) {
     RC_WG_MARK(c.ws, c.wo.total, RC_KID_EMB_BWD, 0);
     if (e >= nnode + head) {
-      rc_wait_leads(c, c.ws + r * c.wss, cnt, KP);
+      rc_wait_leads(c, c.ws + r * c.wss, cnt, RC_PUB_ALL, KP);  // the dA records come with stage 2
       emb_bwd_dadj(c, r, e - nnode - head, true);
     } else if (e == nnode) {
       emb_bwd_head(c, r, sm);
@@ -1069,7 +1073,15 @@ void k_bwd_merged(StepCtx c, int nUl, int nQ, int nnode, int head, int nred,
     uc = rem / nQ;
     qc = rem - uc * nQ;
   }
-  fac_bwd_wg(c, nUl, nQ, kj, uc, qc, r, sm, e < 0 ? cnt : nullptr, role);
+  // The factor workgroups are the launch's longest chain and its younger waves: on a SIMD they share
+  // with a node workgroup's wave (dispatched earlier) they lose the issue arbitration whenever the
+  // node wave is awake.  One static priority above the node waves' 0, never flipped.  (The guide's
+  // "static priority for the younger half", MI355X_MICROARCH.md, is about the two halves of one
+  // 8-wave workgroup; applying it to waves of two workgroups on one SIMD is this project's own
+  // extrapolation, carried by the single-fit A/B of DESIGN 7.1 round 9 alone -- so the single
+  // sub-block kernel only: no pack has been measured with it.)
+  if (!MULTI) __builtin_amdgcn_s_setprio(RC_MERGED_FAC_PRIO);
+  fac_bwd_wg<true>(c, nUl, nQ, kj, uc, qc, r, sm, e < 0 ? cnt : nullptr, role);
 }
 
 // ---- adjacency algebra for p <= 64 in one workgroup, operands in LDS with row stride P = p + 1

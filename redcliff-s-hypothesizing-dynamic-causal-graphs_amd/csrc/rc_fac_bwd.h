@@ -54,12 +54,17 @@ __device__ inline void rc_adam_pre(const StepCtx& c, float* P, float* M, float* 
 }
 
 // One workgroup (network kj, hidden chunk uc, dW0 column tile qc) of replica r.  publish != nullptr
-// (the merged backward launch, k_bwd_merged): the lead workgroup of each network signals, after
-// its dL/dw partials, group norms and dL/dA records are in memory, by an agent-scope release and
-// an increment of *publish (the embedder-backward workgroups of the same launch wait for all K*p).
+// (the merged backward launch, k_bwd_merged): the lead workgroup of each network signals twice on
+// *publish (rc_publish: write-through stores drained, then one count) -- stage 1 once its dL/dw
+// partials are in memory (the node workgroups of the same launch wait for all K*p of these),
+// stage 2 once its dL/dA records are (the dA-reduce workgroups wait for those).
 // role (split-lead step, rc_capi.hip): RC_FB_ALL = records and update; RC_FB_RECORDS = the lead's
 // records only (one workgroup per network, returns before the update); RC_FB_UPDATE = the update
 // only (no workgroup writes the records).  The arithmetic of every part is the same in each role.
+// MERGED (k_bwd_merged's instantiation): the update epilogue in the order and lane mapping that
+// measured faster there; k_fac_bwd keeps the other one, in which it measured faster (DESIGN 7.1,
+// round 9).  The same sums in the same order either way.
+template <bool MERGED>
 __device__ __forceinline__ void fac_bwd_wg(const StepCtx& c, int nUl, int nQ, int kj, int uc, int qc, int r, float* sm,
                            unsigned* publish, int role = RC_FB_ALL) {
   const RedcliffDims& d = c.d;
@@ -131,7 +136,11 @@ __device__ __forceinline__ void fac_bwd_wg(const StepCtx& c, int nUl, int nQ, in
   // (32-bit offsets inside the replica's factor slice: K p h p L <= 2^29 floats at the engine's limits)
   const int kjW0 = (int)c.fo.W0 + kj * h * Q;
   float pw[4] = {0.f, 0.f, 0.f, 0.f}, pm[4] = {0.f, 0.f, 0.f, 0.f}, pv[4] = {0.f, 0.f, 0.f, 0.f};
+  // the small parameters' Adam state, on the lanes that reduce and update them.  MERGED: b0 of unit
+  // u0 + lane on lanes 0-15, W1 of unit u0 + lane - 16 on lanes 16-31 (sb[0..2]), b1 on wave 1's
+  // first lane (s1); otherwise b0 and W1 of unit u0 + lane on lanes 0-15 (sb[0..2], sb[3..5]), b1 on lane 0
   float sb[6] = {0.f, 0.f, 0.f, 0.f, 0.f, 0.f}, s1[3] = {0.f, 0.f, 0.f};
+  const int b1lane = MERGED ? 64 : 0;
   const bool gonly = c.flags & RC_GRAD_ONLY;
   const bool split = lead && publish != nullptr;
   auto adam_loads = [&]() {
@@ -144,12 +153,17 @@ __device__ __forceinline__ void fac_bwd_wg(const StepCtx& c, int nUl, int nQ, in
           pw[jj] = P[idx]; pm[jj] = PM[idx]; pv[jj] = PV[idx];
         }
       }
-      if (qc == 0 && tid < FAC_UC && u0 + tid < h) {
+      if (MERGED) {
+        if (qc == 0 && tid < 2 * FAC_UC && u0 + fl15 < h) {
+          const int is = (int)(tid < FAC_UC ? c.fo.b0 : c.fo.W1) + kj * h + u0 + fl15;
+          sb[0] = P[is]; sb[1] = PM[is]; sb[2] = PV[is];
+        }
+      } else if (qc == 0 && tid < FAC_UC && u0 + tid < h) {
         const int ib = (int)c.fo.b0 + kj * h + u0 + tid, iw = (int)c.fo.W1 + kj * h + u0 + tid;
         sb[0] = P[ib]; sb[1] = PM[ib]; sb[2] = PV[ib];
         sb[3] = P[iw]; sb[4] = PM[iw]; sb[5] = PV[iw];
       }
-      if (qc == 0 && uc == 0 && tid == 0) {
+      if (qc == 0 && uc == 0 && tid == b1lane) {
         const int i1 = (int)c.fo.b1 + kj;
         s1[0] = P[i1]; s1[1] = PM[i1]; s1[2] = PV[i1];
       }
@@ -238,7 +252,10 @@ __device__ __forceinline__ void fac_bwd_wg(const StepCtx& c, int nUl, int nQ, in
     if (lead && adj_grad) tpart[b] = g * ybuf[b * K + k];  // forecast part, adjacency part added below
     if (lead && k == 0) {
       fsum += res * res;
-      ws[c.wo.xsim + (int64_t)b * p + j] = xs;
+      if (split)
+        xt[b] = xs;  // x_sim leaves after the stage-1 publish (the slot is this thread's, consumed above)
+      else
+        ws[c.wo.xsim + (int64_t)b * p + j] = xs;
     }
   }
   // ---- group norms G[kj][c][t] (cmlp.py:147-167)
@@ -246,14 +263,14 @@ __device__ __forceinline__ void fac_bwd_wg(const StepCtx& c, int nUl, int nQ, in
     const float g = sqrtf(sqs[e]);
     Gs[e] = g;
     dGs[e] = 0.f;
-    if (lead) ws[c.wo.G + (int64_t)kj * Q + e] = g;
+    if (lead && !split) ws[c.wo.G + (int64_t)kj * Q + e] = g;
   }
   if (values && lead && k == 0) {
     const float t = rc_block_sum(fsum, red);
     if (tid == 0) ws[c.wo.lossp + j] = t;
   }
   __syncthreads();
-  if (lead)
+  if (lead && !split)
     for (int cc = tid; cc < p; cc += RC_BLOCK) {
       float sq = 0.f;
       for (int t = 0; t < L; ++t) sq += sqs[cc * L + t];
@@ -300,6 +317,27 @@ __device__ __forceinline__ void fac_bwd_wg(const StepCtx& c, int nUl, int nQ, in
     if (values) {
       const float tv = rc_block_sum(v, red);
       if (tid == 0) ws[c.wo.lossp + p + kj] = hy.c_adj * tv;
+    }
+  }
+  // Merged launch, stage 1 of the lead's publish: the node workgroups read only the dL/dw
+  // partials, so the lead counts itself in as soon as the last of them is stored -- by part 2's
+  // window sums with the adjacency loss, by part 1 without it (part 2 is then skipped, so this one
+  // placement serves both) -- and everything no node workgroup reads (x_sim, G, G0, dL/dG / dL/dA)
+  // follows.
+  if (split) {
+    RC_PHASE(c.ws, c.wo.total, blockIdx.x, 24);
+    RC_WG_MARK(c.ws, c.wo.total, RC_KID_EMB_WAIT, 0);  // trace builds: a lead's stage-1 time (its start slot)
+    rc_publish(publish, RC_PUB_DWP);
+    RC_PHASE(c.ws, c.wo.total, blockIdx.x, 25);
+  }
+  if (split) {  // the records nothing in the merged launch reads: x_sim, G, the G0 row sums
+    if (k == 0)
+      for (int b = tid; b < B; b += RC_BLOCK) ws[c.wo.xsim + (int64_t)b * p + j] = xt[b];
+    for (int e = tid; e < Q; e += RC_BLOCK) ws[c.wo.G + (int64_t)kj * Q + e] = Gs[e];
+    for (int cc = tid; cc < p; cc += RC_BLOCK) {
+      float sq = 0.f;
+      for (int t = 0; t < L; ++t) sq += sqs[cc * L + t];
+      ws[c.wo.G0 + (int64_t)kj * p + cc] = sqrtf(sq);
     }
   }
   if (adj_grad) {
@@ -350,7 +388,7 @@ __device__ __forceinline__ void fac_bwd_wg(const StepCtx& c, int nUl, int nQ, in
   RC_PHASE(c.ws, c.wo.total, blockIdx.x, 18);
   if (publish && lead) {
     RC_WG_MARK(c.ws, c.wo.total, RC_KID_EMB_WAIT, 1);  // trace builds: the lead's publish time (end slot)
-    rc_publish(publish);
+    rc_publish(publish, RC_PUB_ALL);  // stage 2: the dL/dA records (the reduce workgroups' input) too
   }
   if (!stepB || role == RC_FB_RECORDS) return;
   if (split) {  // the lead's own update operands, after its records are out
@@ -478,25 +516,8 @@ __device__ __forceinline__ void fac_bwd_wg(const StepCtx& c, int nUl, int nQ, in
     }
   }
   RC_PHASE(c.ws, c.wo.total, tbx, 21);
-  if (qc == 0) {
-    rA[tid] = dW1u;
-    rB[tid] = db0u;
-    if (uc == 0) db1 = rc_block_sum(db1, red);
-    __syncthreads();
-    if (tid < 16 && u0 + tid < h) {
-      float g1 = 0.f, g0 = 0.f;
-      for (int s2 = 0; s2 < 16; ++s2) {
-        g1 += rA[s2 * 16 + tid];
-        g0 += rB[s2 * 16 + tid];
-      }
-      rc_adam_pre(c, P, PM, PV, GF, (int)c.fo.b0 + kj * h + u0 + tid, g0, as, sb[0], sb[1], sb[2]);
-      rc_adam_pre(c, P, PM, PV, GF, (int)c.fo.W1 + kj * h + u0 + tid, g1, as, sb[3], sb[4], sb[5]);
-    }
-    if (uc == 0 && tid == 0) rc_adam_pre(c, P, PM, PV, GF, (int)c.fo.b1 + kj, db1, as, s1[0], s1[1], s1[2]);
-  }
-  RC_PHASE(c.ws, c.wo.total, tbx, 22);
-  // dW0 tile: + adjacency-L1 term through the group norms, then Adam
-  {
+  // dW0 tile: + adjacency-L1 term through the group norms (LDS values of part 2), then Adam
+  auto dw0_adam = [&]() {
 #pragma unroll
     for (int jj = 0; jj < 4; ++jj) {
       const int u = u0 + tile_u(jj), q = q0 + tile_q(jj);
@@ -506,6 +527,40 @@ __device__ __forceinline__ void fac_bwd_wg(const StepCtx& c, int nUl, int nQ, in
       if (adj_grad && Gs[q] > 0.f) g += dGs[q] * ((gonly ? P[idx] : pw[jj]) / Gs[q]);
       rc_adam_pre(c, P, PM, PV, GF, idx, g, as, pw[jj], pm[jj], pv[jj]);
     }
+  };
+  // the chunk's b0 / W1 gradients (16 slices per unit, summed in slice order) and b1
+  auto small_adam = [&]() {
+    if (qc != 0) return;
+    rA[tid] = dW1u;
+    rB[tid] = db0u;
+    if (uc == 0) db1 = rc_block_sum(db1, red);
+    __syncthreads();
+    if (MERGED) {  // three groups of lanes side by side: lanes 0-15 b0, lanes 16-31 W1, wave 1's first lane b1
+      if (tid < 2 * FAC_UC && u0 + fl15 < h) {
+        const float* part = tid < FAC_UC ? rB : rA;
+        float g = 0.f;
+        for (int s2 = 0; s2 < 16; ++s2) g += part[s2 * 16 + fl15];
+        rc_adam_pre(c, P, PM, PV, GF, (int)(tid < FAC_UC ? c.fo.b0 : c.fo.W1) + kj * h + u0 + fl15, g, as, sb[0], sb[1], sb[2]);
+      }
+    } else if (tid < 16 && u0 + tid < h) {
+      float g1 = 0.f, g0 = 0.f;
+      for (int s2 = 0; s2 < 16; ++s2) {
+        g1 += rA[s2 * 16 + tid];
+        g0 += rB[s2 * 16 + tid];
+      }
+      rc_adam_pre(c, P, PM, PV, GF, (int)c.fo.b0 + kj * h + u0 + tid, g0, as, sb[0], sb[1], sb[2]);
+      rc_adam_pre(c, P, PM, PV, GF, (int)c.fo.W1 + kj * h + u0 + tid, g1, as, sb[3], sb[4], sb[5]);
+    }
+    if (uc == 0 && tid == b1lane) rc_adam_pre(c, P, PM, PV, GF, (int)c.fo.b1 + kj, db1, as, s1[0], s1[1], s1[2]);
+  };
+  if (MERGED) {  // the workgroup's bulk stores first: they drain under the small reduction
+    dw0_adam();
+    RC_PHASE(c.ws, c.wo.total, tbx, 22);
+    small_adam();
+  } else {
+    small_adam();
+    RC_PHASE(c.ws, c.wo.total, tbx, 22);
+    dw0_adam();
   }
   RC_PHASE(c.ws, c.wo.total, tbx, 23);
   RC_WG_MARK(c.ws, c.wo.total, RC_KID_FAC_BWD, 1);

@@ -26,7 +26,7 @@ __global__ __launch_bounds__(RC_BLOCK) void k_fac_bwd(StepCtx c, int nUl, int nQ
   const int kj = per == 1 ? (int)blockIdx.x : (int)blockIdx.x / per;
   const int rem0 = blockIdx.x - kj * per;
   const int uc = nQ == 1 ? rem0 : rem0 / nQ, qc = rem0 - uc * nQ;
-  fac_bwd_wg(c, nUl, nQ, kj, uc, qc, rc_rep(c, blockIdx.y), sm, nullptr, role);
+  fac_bwd_wg<false>(c, nUl, nQ, kj, uc, qc, rc_rep(c, blockIdx.y), sm, nullptr, role);
 }
 
 // Finished predictions of the stand-alone forward: out[r][b][k][j] = sum over the nU hidden-chunk

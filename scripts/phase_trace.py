@@ -47,12 +47,19 @@ def main():
     tot = eng.ws_off["total"]
     tr = eng.ws[tot - 32768:tot].cpu().numpy().view(np.uint64).astype(np.int64).reshape(8, 2048)
     names = ["emb_fwd", "fac_fwd", "fac_bwd", "emb_bwd", "emb_final", "fac_mix"]
-    # merged backward: node workgroups' wait-return times (kid 7, start slots only)
-    wt = tr[7][0::2]
+    # merged backward (kid 7): start slots of the K*p leads = their stage-1 publish (dL/dw stored), of
+    # the node workgroups behind them = their wait's return; end slots of the leads = stage 2
+    KP = c["K"] * c["p"]
+    wt = tr[7][0::2][KP:]
     wt = wt[wt > 0]
+    pub1 = tr[7][0::2][:KP]
+    pub1 = pub1[pub1 > 0]
     t_first = min(int(tr[k][0::2][tr[k][0::2] > 0].min()) for k in range(len(names)) if (tr[k][0::2] > 0).any())
     ph = tr[6]
-    for lo, hi, label in ((0, 16, "emb_fwd WG0 phases"), (16, 32, "fac_bwd WG0 phases"), (32, 48, "emb_bwd WG0 phases"),
+    if ph[24] > 0 and ph[16] > 0:  # lead 0 of a merged launch: its marks in time order, us after mark 16
+        print("fac_bwd lead 0 marks (us after 16; 24 / 25 = before / after the stage-1 publish, 18 = before stage 2): " +
+              "  ".join("%d %.2f" % (i, (ph[i] - ph[16]) / 100.0) for i in sorted((17, 24, 25, 18), key=lambda i: ph[i]) if ph[i] > 0))
+    for lo, hi, label in ((0, 16, "emb_fwd WG0 phases"), (16, 24, "fac_bwd WG0 phases"), (32, 48, "emb_bwd WG0 phases"),
                             (48, 64, "emb_final adjacency WG phases")):
         t = ph[lo:hi]
         idx = [i for i in range(hi - lo) if t[i] > 0]
@@ -95,8 +102,12 @@ def main():
             lo = hi
     pub = tr[7][1::2]
     pub = pub[pub > 0]
+    if pub1.size:
+        print("factor leads published stage 1, dL/dw (merged backward): %d leads, first %.2f us  median %.2f  last %.2f"
+              % (pub1.size, (pub1.min() - t_first) / 100.0, (np.median(pub1) - t_first) / 100.0,
+                 (pub1.max() - t_first) / 100.0))
     if pub.size:
-        print("factor leads published (merged backward): %d leads, first %.2f us  median %.2f  last %.2f"
+        print("factor leads published (merged backward; stage 2, every record): %d leads, first %.2f us  median %.2f  last %.2f"
               % (pub.size, (pub.min() - t_first) / 100.0, (np.median(pub) - t_first) / 100.0,
                  (pub.max() - t_first) / 100.0))
         order = np.argsort(tr[7][1::2])[::-1][:5]
