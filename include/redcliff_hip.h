@@ -729,6 +729,64 @@ int redcliff_dgcnn_fit_supported(const RedcliffDims* d);
 int64_t redcliff_dgcnn_fit_ws_floats(const RedcliffDims* d, int32_t B, int64_t N);
 int redcliff_dgcnn_fit_run(const RedcliffDgcnnFitArgs* a, void* stream);
 
+/* The supervised dCSFA-NMF baseline (models/dcsfa_nmf.py: deep encoder, MSE reconstruction, "Residual"
+ * supervised reconstruction, one intercept, no correlation constraints) as a stand-alone fit: one call
+ * enqueues every AdamW step of an epoch (additive to ABI 10).
+ * Each of the R models owns a packed block at par + r*par_stride (par_m / par_v: AdamW's exp_avg /
+ * exp_avg_sq in the same layout):
+ *   W_nmf[K][D] | W1[H][D] | b1[H] | bn_w[H] | bn_b[H] | W2[K][H] | b2[K] | phi[ns] | beta[ns]
+ * bn_rm / bn_rv: [R][H] running statistics.  X [N][D], Y [N][ns], TM [N][ns] (the task mask as floats),
+ * PW [N] (the prediction weights); replica r reads them at + r*stride (0: shared).
+ * Arithmetic of one step over the Bi rows idx[s*B .. s*B + Bi) (indices outside [0, N) are clamped):
+ *   z = x W1^T + b1 (summed in double, rounded once); BatchNorm over the batch (statistics in double, the biased variance normalises, the
+ *   unbiased one goes to the running variance with bn_momentum); a = LeakyReLU(0.01); pre = a W2^T + b2
+ *   (slices of 8 hidden units ascending, then b2); s = softplus(pre) (threshold 20); Wp = softplus(W_nmf);
+ *   mse = sum (s Wp - x)^2 / (Bi D);  s_h = ((x - s_un Wp_un) Wp_sup^T) inv(Wp_sup Wp_sup^T);
+ *   res = ||s_sup - s_h||_F / (1 - c exp(-||s_h||_F)), both norms over the whole batch;
+ *   y_pred = sigmoid(s_j phi_j + beta_j); bce = mean of -PW (t log p + (1 - t) log(1 - p)), p = y_pred TM,
+ *   t = Y TM, the logs clamped at -100.
+ *   loss[r][s][0] = recon_weight mse + sup_recon_weight res;  loss[r][s][1] = sup_weight bce.
+ * REDCLIFF_DCSFA_TRAIN differentiates their sum and applies torch.optim.AdamW (decoupled decay) at step
+ * number tB + s to every parameter.  REDCLIFF_DCSFA_PRETRAIN differentiates loss[..][0] only and leaves
+ * W_nmf, phi, beta and their moments untouched (they have no gradient: no decay, no state).  Both: three
+ * launches per step on the one stream (per-slice forward; head; per-slice backward); launch boundaries are
+ * the only cross-workgroup dependencies.  num_batches_tracked is the caller's.
+ * REDCLIFF_DCSFA_EVAL: eval mode (running statistics) over rows [row0, row0 + n) in batches of B; batch s
+ * writes ev[r][s][0] = its sum of squared reconstruction errors and ev[r][s][1 + 4j ..] = TP, FP, TN, FN of
+ * supervised network j over the rows with TM == 1 (label Y >= 0.6, prediction y_pred >= 0.6).
+ * ws: R * redcliff_dcsfa_ws_floats(H, K, B) floats, 8-byte aligned.
+ * Limits: K <= 8, 1 <= ns <= K, Bmax <= 128, R <= 256, D, H <= 4096 and
+ *   max(128 + 9 Bmax + 40 (D|1), 128 + Bmax + 7 Bmax K + 4 K K + K (D|1)) <= 40960 floats of LDS;
+ * outside them REDCLIFF_ELIMIT (the query returns 0).  A last batch of one row (no batch statistics), null
+ * buffers, a bad mode, B < 1 or > Bmax, negative strides: REDCLIFF_EINVAL.  All checks precede any HIP call.
+ * Every sum's order is fixed by the shape and the batch size: a replica's bits do not depend on R. */
+#define REDCLIFF_DCSFA_TRAIN 0
+#define REDCLIFF_DCSFA_PRETRAIN 1
+#define REDCLIFF_DCSFA_EVAL 2
+typedef struct RedcliffDcsfaArgs {
+  int32_t D, H, K, ns, R, Bmax;
+  int32_t mode, B, tB, pad_;     /* tB: AdamW step number of the first step (1-based)                     */
+  int64_t N;                     /* rows of one data set                                                  */
+  int64_t n;                     /* TRAIN / PRETRAIN: drawn rows of the epoch; EVAL: rows from row0       */
+  int64_t row0;                  /* EVAL only (0 otherwise)                                               */
+  const float* X; int64_t x_pstride;
+  const float* Y; const float* TM; int64_t y_pstride;
+  const float* PW; int64_t pw_pstride;
+  const int32_t* idx; int64_t idx_pstride;   /* [R][n] the epoch's drawn rows (EVAL: unused)              */
+  float* par; float* par_m; float* par_v; int64_t par_stride;
+  float* bn_rm; float* bn_rv;                /* [R][H]                                                    */
+  double lr, weight_decay, beta1, beta2, eps, bn_eps, bn_momentum;
+  float recon_weight, sup_weight, sup_recon_weight, sup_smoothness_weight;
+  float* loss;                   /* TRAIN / PRETRAIN: [R][nsteps][2]                                      */
+  double* ev;                    /* EVAL: [R][nbatches][1 + 4 ns]                                         */
+  float* ws; size_t ws_bytes;
+} RedcliffDcsfaArgs;
+/* Host-only limit query: 0 outside the limits (with a redcliff_last_error message), else the workgroup's
+ * LDS footprint in floats. */
+int redcliff_dcsfa_supported(int32_t D, int32_t H, int32_t K, int32_t ns, int32_t Bmax, int32_t R);
+int64_t redcliff_dcsfa_ws_floats(int32_t H, int32_t K, int32_t B);
+int redcliff_dcsfa_run(const RedcliffDcsfaArgs* a, void* stream);
+
 /* Per-kernel HIP-event timing for benchmarking: redcliff_kernel_timing(1) brackets every
  * kernel launched by redcliff_train_step with events on its stream; redcliff_kernel_times()
  * synchronises them and returns per-kernel totals (ids 0..11: supports, emb_fwd, fac_fwd,

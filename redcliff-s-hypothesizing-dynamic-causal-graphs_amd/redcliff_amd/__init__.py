@@ -16,9 +16,11 @@ from .clstm import LSTM, cLSTM
 from .clstm_fm import cLSTM_FM, fit_lstm_baselines
 from .navar import NAVAR, fit_navar_baselines
 from .navar_lstm import NAVARLSTM, fit_navar_lstm_baselines
+from .dcsfa_nmf import DcsfaFitPack, DcsfaNmf, FullDCSFAModel, FullDCSFAModel_GCv2, NmfBase, fit_dcsfa_baselines
 
 __all__ = ["MLP", "cMLP", "DGCNN", "DGCNN_Model", "DGCNN_Embedder", "cEmbedder", "MLPClassifierForSingleObjective",
            "MLPClassifierForMultipleObjectives", "REDCLIFF_S_CMLP", "REDCLIFF_S_CMLP_withStateSmoothing", "ReplicaPack",
            "PerReplica", "fit_packs", "grid_packs", "shard_grid", "DataParallelFit",
            "score_recordings", "cMLP_FM", "fit_baselines", "LSTM", "cLSTM", "cLSTM_FM", "fit_lstm_baselines",
-           "NAVAR", "fit_navar_baselines", "NAVARLSTM", "fit_navar_lstm_baselines", "fit_dgcnn_baselines"]
+           "NAVAR", "fit_navar_baselines", "NAVARLSTM", "fit_navar_lstm_baselines", "fit_dgcnn_baselines",
+           "NmfBase", "DcsfaNmf", "FullDCSFAModel", "FullDCSFAModel_GCv2", "DcsfaFitPack", "fit_dcsfa_baselines"]

@@ -47,7 +47,8 @@ EXPORTED = ("redcliff_abi_version", "redcliff_last_error", "redcliff_workspace_b
             "redcliff_fm_supported", "redcliff_fm_run", "redcliff_lstm_fm_supported", "redcliff_lstm_fm_run",
             "redcliff_navar_supported", "redcliff_navar_run",
             "redcliff_navar_lstm_supported", "redcliff_navar_lstm_ws_floats", "redcliff_navar_lstm_run",
-            "redcliff_dgcnn_fit_supported", "redcliff_dgcnn_fit_ws_floats", "redcliff_dgcnn_fit_run")
+            "redcliff_dgcnn_fit_supported", "redcliff_dgcnn_fit_ws_floats", "redcliff_dgcnn_fit_run",
+            "redcliff_dcsfa_supported", "redcliff_dcsfa_ws_floats", "redcliff_dcsfa_run")
 CEMB_WS_REGIONS = ("ha", "w1", "g", "g0", "E", "E0", "dE", "draw")
 KERNEL_IDS = ("supports", "emb_fwd", "fac_fwd", "fac_bwd", "emb_bwd", "emb_final", "fac_mix", "emb_combine", "fac_lead",
               "score", "score_graphs", "score_cemb")
@@ -161,6 +162,17 @@ class DgcnnFitArgs(ctypes.Structure):
                 ("ws", _vp), ("ws_bytes", ctypes.c_size_t), ("replicas", _vp), ("n_replicas", ctypes.c_int32)]
 
 
+class DcsfaArgs(ctypes.Structure):
+    """RedcliffDcsfaArgs (redcliff_dcsfa_run)."""
+    _fields_ = [(n, ctypes.c_int32) for n in ("D", "H", "K", "ns", "R", "Bmax", "mode", "B", "tB", "pad_")] + [
+        ("N", _i64), ("n", _i64), ("row0", _i64), ("X", _vp), ("x_pstride", _i64), ("Y", _vp), ("TM", _vp),
+        ("y_pstride", _i64), ("PW", _vp), ("pw_pstride", _i64), ("idx", _vp), ("idx_pstride", _i64),
+        ("par", _vp), ("par_m", _vp), ("par_v", _vp), ("par_stride", _i64), ("bn_rm", _vp), ("bn_rv", _vp)] + [
+        (n, ctypes.c_double) for n in ("lr", "weight_decay", "beta1", "beta2", "eps", "bn_eps", "bn_momentum")] + [
+        (n, ctypes.c_float) for n in ("recon_weight", "sup_weight", "sup_recon_weight", "sup_smoothness_weight")] + [
+        ("loss", _vp), ("ev", _vp), ("ws", _vp), ("ws_bytes", ctypes.c_size_t)]
+
+
 def adam_hyper(lr, betas, eps, weight_decay):
     b1, b2 = float(betas[0]), float(betas[1])
     return AdamHyper(float(lr), b1, b2, float(eps), float(weight_decay), b2, 1.0 - b1, 1.0 - b2, 0)
@@ -241,12 +253,15 @@ def lib():
     L.redcliff_dgcnn_fit_supported.argtypes = [ctypes.POINTER(Dims)]
     L.redcliff_dgcnn_fit_ws_floats.argtypes = [ctypes.POINTER(Dims), ctypes.c_int32, _i64]
     L.redcliff_dgcnn_fit_run.argtypes = [ctypes.POINTER(DgcnnFitArgs), _vp]
+    L.redcliff_dcsfa_supported.argtypes = [ctypes.c_int32] * 6
+    L.redcliff_dcsfa_ws_floats.argtypes = [ctypes.c_int32] * 3
+    L.redcliff_dcsfa_run.argtypes = [ctypes.POINTER(DcsfaArgs), _vp]
     for name in EXPORTED[2:]:
         if name not in ("redcliff_workspace_bytes", "redcliff_emb_param_count", "redcliff_fac_param_count",
                         "redcliff_build_id", "redcliff_cemb_param_count", "redcliff_cemb_workspace_bytes",
                         "redcliff_score_recording_workspace_bytes",
                         "redcliff_score_recording_pack_workspace_bytes", "redcliff_navar_lstm_ws_floats",
-                        "redcliff_dgcnn_fit_ws_floats"):
+                        "redcliff_dgcnn_fit_ws_floats", "redcliff_dcsfa_ws_floats"):
             getattr(L, name).restype = ctypes.c_int
     L.redcliff_cemb_param_count.restype = ctypes.c_size_t
     L.redcliff_cemb_workspace_bytes.restype = ctypes.c_size_t
@@ -254,6 +269,7 @@ def lib():
     L.redcliff_score_recording_pack_workspace_bytes.restype = ctypes.c_size_t
     L.redcliff_navar_lstm_ws_floats.restype = ctypes.c_int64
     L.redcliff_dgcnn_fit_ws_floats.restype = ctypes.c_int64
+    L.redcliff_dcsfa_ws_floats.restype = ctypes.c_int64
     L.redcliff_build_id.restype = ctypes.c_char_p
     if L.redcliff_abi_version() != ABI_VERSION:
         raise ImportError("libredcliff_hip.so ABI %d != %d" % (L.redcliff_abi_version(), ABI_VERSION))

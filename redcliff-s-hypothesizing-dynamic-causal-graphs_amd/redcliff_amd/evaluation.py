@@ -257,8 +257,10 @@ def get_model_gc_estimates(model, model_type, num_ests_required, X=None):
     """REDCLIFF branch of eval_utils.py:908-925: the primary-mode GC of the single sample
     in ``X`` (lagged, unthresholded), one (p, p, L') array per factor, replicated when the
     mode yields one graph."""
+    if "DCSFA" in model_type:  # eval_utils.py:936-937: one (nodes, nodes) array per factor
+        return model.GC(threshold=False, ignore_features=True)
     if "REDCLIFF" not in model_type:
-        raise NotImplementedError("only REDCLIFF models are part of this build (model_type=%r)" % model_type)
+        raise NotImplementedError("only REDCLIFF and DCSFA models are part of this build (model_type=%r)" % model_type)
     by_sample = model.GC(model.primary_gc_est_mode, X=X, threshold=False, ignore_lag=False,
                          combine_wavelet_representations=True, rank_wavelets=False)
     assert len(by_sample) == 1
