@@ -180,6 +180,16 @@ int redcliff_train_step(const RedcliffStepArgs* a, void* stream);
  * corresponding RC_STEP_* flag is set.  RC_REFRESH_SUPPORTS applies to the first step. */
 int redcliff_train_steps(const RedcliffStepArgs* a, int32_t nsteps, const int64_t* rows, const int32_t* sizes,
                          int32_t bn_stats_step, void* stream);
+/* redcliff_train_steps / redcliff_cemb_train_steps of at least 4 steps evaluate the Adam bias
+ * corrections of the call's steps once per chunk of steps (one small launch on `stream`) into a table at the end of every
+ * replica's workspace slice, which the step kernels read instead of computing them per
+ * workgroup; a direct redcliff_train_step computes them in the kernels.  Same device arithmetic,
+ * same bits.  REDCLIFF_ADAM_TABLE=0 (read per call) switches the table off;
+ * REDCLIFF_ADAM_TABLE_SMAX=n shortens the chunk (tests).  Additive: REDCLIFF_ABI_VERSION stays 10.
+ * out[0] = the table's offset (floats) in a replica's slice, out[1] = steps per chunk in effect,
+ * out[2] = floats per entry (neg_step bc2s eps wd b2 omb1 omb2 pad); entry (step i of the chunk,
+ * group g: 0 = A, 1 = B) starts at out[0] + (2 i + g) * out[2]. */
+int redcliff_adam_table_layout(const RedcliffDims* d, int64_t* out);
 
 /* Offsets (floats, per replica) of the workspace regions: T R f1 w a y G G0 w1 dwp dAadj dWi dS
  * dgb S dZ amat lossp xsim gfc total.  Returns the number of offsets available.  The host reads

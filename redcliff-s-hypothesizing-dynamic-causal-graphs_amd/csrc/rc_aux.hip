@@ -98,7 +98,30 @@ __global__ __launch_bounds__(RC_BLOCK) void k_adam_apply(float* P, float* M, flo
   }
 }
 
+// The Adam table of one redcliff_train_steps chunk (WsOff.adamt): one thread per (step i < n of
+// the chunk, replica r < R, group g): entry tab[r * wss + (2 i + g) * 8] = rc_adam_scalars of
+// hyp[r].A / .B at step number tA0 + i * incA / tB0 + i * incB (inc = 1 for a group that steps, else
+// 0) -- the function the kernels evaluated per workgroup, so the same device pow and the same bits.
+__global__ __launch_bounds__(RC_BLOCK) void k_adam_table(const RedcliffReplicaHyper* hyp, int R, int n, int tA0, int incA,
+                                                         int tB0, int incB, float* tab, int64_t wss) {
+  const int id = blockIdx.x * RC_BLOCK + threadIdx.x;
+  if (id >= 2 * n * R) return;
+  const int g = id & 1, ir = id >> 1, r = ir % R, i = ir / R;
+  const RcAdamScalars s = g ? rc_adam_scalars(hyp[r].B, tB0 + i * incB) : rc_adam_scalars(hyp[r].A, tA0 + i * incA);
+  float* e = tab + (int64_t)r * wss + (2 * i + g) * RC_ADAM_ENTRY;
+  e[0] = s.neg_step; e[1] = s.bc2s; e[2] = s.eps; e[3] = s.wd; e[4] = s.b2; e[5] = s.omb1; e[6] = s.omb2;
+  e[7] = 0.f;
+}
+
 }  // namespace
+
+int rc_launch_adam_table(const RedcliffReplicaHyper* hyp, int R, int n, int tA0, int incA, int tB0, int incB, float* tab,
+                         int64_t wss, hipStream_t s) {
+  if (n < 1 || n > RC_ADAM_SMAX) { rc_set_error("adam table: %d steps outside [1, %d]", n, RC_ADAM_SMAX); return REDCLIFF_EINVAL; }
+  const int nb = (2 * n * R + RC_BLOCK - 1) / RC_BLOCK;
+  hipLaunchKernelGGL(k_adam_table, dim3(nb), dim3(RC_BLOCK), 0, s, hyp, R, n, tA0, incA, tB0, incB, tab, wss);
+  return rc_check(hipGetLastError(), "k_adam_table");
+}
 
 extern "C" int redcliff_adam_apply(const RedcliffDims* d, float* params, float* exp_avg, float* exp_avg_sq,
                                    const float* grad, int64_t n, int64_t stride, const RedcliffReplicaHyper* hyper,

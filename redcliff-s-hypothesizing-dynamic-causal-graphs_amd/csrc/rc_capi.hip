@@ -311,12 +311,57 @@ static int make_ctx(const RedcliffStepArgs* a, StepCtx& c, bool cemb = false) {
   return 0;
 }
 
-int redcliff_train_step(const RedcliffStepArgs* a, void* stream) {
+static int adam_table_smax() {
+  const char* sv = getenv("REDCLIFF_ADAM_TABLE_SMAX");
+  const int n = sv ? atoi(sv) : 0;
+  return n >= 1 && n < RC_ADAM_SMAX ? n : RC_ADAM_SMAX;
+}
+
+int redcliff_adam_table_layout(const RedcliffDims* d, int64_t* out) {
+  if (check_dims(d) != 0 || !out) return REDCLIFF_EINVAL;
+  out[0] = rc_ws_off(*d).adamt;
+  out[1] = adam_table_smax();
+  out[2] = RC_ADAM_ENTRY;
+  return 0;
+}
+
+// Steps per Adam-table chunk of a redcliff_train_steps call, 0 = no table: a call that steps no
+// group with Adam, a call of fewer than RC_ADAM_TABLE_MIN_STEPS steps (batch_update is a call of
+// ONE step: the table's launch, some microseconds on the stream, would cost it more than the
+// ~1-3 us a step's chains save; from 4 steps on the launch is paid back), REDCLIFF_ADAM_TABLE=0
+// (read per call: the kernels then compute the scalars as a direct redcliff_train_step does), or
+// arguments the step itself will reject.
+// REDCLIFF_ADAM_TABLE_SMAX shortens the chunk below RC_ADAM_SMAX (tests: forces refills).
+#define RC_ADAM_TABLE_MIN_STEPS 4
+static int adam_table_chunk(const RedcliffStepArgs* a, const RedcliffDims& d, int nsteps) {
+  if (nsteps < RC_ADAM_TABLE_MIN_STEPS || !(a->flags & (RC_STEP_A | RC_STEP_B)) || (a->flags & RC_GRAD_ONLY)) return 0;
+  const char* v = getenv("REDCLIFF_ADAM_TABLE");
+  if (v && !strcmp(v, "0")) return 0;
+  if (check_dims(&d) != 0 || !a->ws || !a->hyper || a->ws_bytes < sizeof(float) * (size_t)rc_ws_off(d).total * (size_t)d.R)
+    return 0;
+  return adam_table_smax();
+}
+// Before step i of nsteps when it opens a chunk: k_adam_table for steps [i, i + chunk) on the
+// caller's stream.  tA / tB advance as in the step loops: only for a group that steps.
+static int adam_table_fill(const RedcliffStepArgs* a, const RedcliffDims& d, int chunk, int i, int nsteps, void* stream) {
+  if (chunk <= 0 || i % chunk != 0) return 0;
+  const int incA = (a->flags & RC_STEP_A) ? 1 : 0, incB = (a->flags & RC_STEP_B) ? 1 : 0;
+  const WsOff wo = rc_ws_off(d);
+  return rc_launch_adam_table(a->hyper, d.R, nsteps - i < chunk ? nsteps - i : chunk, a->tA + incA * i, incA,
+                              a->tB + incB * i, incB, (float*)a->ws + wo.adamt, wo.total, (hipStream_t)stream);
+}
+
+// adam_idx: the step's entry in the Adam table of its redcliff_train_steps chunk, -1 = no table
+static int train_step(const RedcliffStepArgs* a, void* stream, int adam_idx) {
   if (!a) { rc_set_error("null step arguments"); return REDCLIFF_EINVAL; }
   StepCtx c;
   int e = make_ctx(a, c);
   if (e) return e;
   if (c.nrep == 0) return 0;  // every replica of the pack has stopped
+  if (adam_idx >= 0) {
+    c.adt = c.ws + c.wo.adamt;
+    c.adi = adam_idx;
+  }
   static const bool wait_dbg = [] {
     const char* v = getenv("REDCLIFF_DEBUG_WAIT_TIMEOUT");
     return v && strcmp(v, "0") != 0;
@@ -478,6 +523,8 @@ int redcliff_train_step(const RedcliffStepArgs* a, void* stream) {
   return 0;
 }
 
+int redcliff_train_step(const RedcliffStepArgs* a, void* stream) { return train_step(a, stream, -1); }
+
 // Data-parallel update (reference: the optimizer steps of batch_update, models/redcliff_s_cmlp_
 // withStateSmoothing.py:741-759, applied to gradients summed over the ranks): the same step
 // arguments the shard step ran with, after the all-reduce of grad_emb / grad_fac.
@@ -501,6 +548,11 @@ int redcliff_train_steps(const RedcliffStepArgs* a, int32_t nsteps, const int64_
                          int32_t bn_stats_step, void* stream) {
   if (!a || nsteps < 0 || (nsteps > 0 && (!rows || !sizes))) { rc_set_error("train_steps: bad arguments"); return REDCLIFF_EINVAL; }
   RedcliffStepArgs s = *a;
+  // The Adam bias corrections of every step of the call, once per chunk of steps, on the caller's
+  // stream ahead of the chunk's first step: every later launch of the chunk is ordered behind it
+  // (a forked step's second stream through the fork event recorded on this stream after it), and
+  // a refill behind the previous chunk's last step, whose second stream has joined by then.
+  const int chunk = adam_table_chunk(a, a->d, nsteps);
   for (int32_t i = 0; i < nsteps; ++i) {
     s.row0 = rows[i];
     s.B = sizes[i];
@@ -508,7 +560,8 @@ int redcliff_train_steps(const RedcliffStepArgs* a, int32_t nsteps, const int64_
     s.tA = a->tA + ((a->flags & RC_STEP_A) ? i : 0);
     s.tB = a->tB + ((a->flags & RC_STEP_B) ? i : 0);
     if (a->bn_stats) s.bn_stats = a->bn_stats + (int64_t)i * bn_stats_step;
-    const int e = redcliff_train_step(&s, stream);
+    int e = adam_table_fill(a, a->d, chunk, i, nsteps, stream);
+    if (!e) e = train_step(&s, stream, chunk > 0 ? i % chunk : -1);
     if (e) return e;
   }
   return 0;
@@ -558,7 +611,7 @@ int redcliff_cemb_workspace_regions(const RedcliffDims* d, int32_t eh, int64_t* 
   return nr;
 }
 
-int redcliff_cemb_train_step(const RedcliffStepArgs* a, const RedcliffCEmbArgs* ce, void* stream) {
+static int cemb_train_step(const RedcliffStepArgs* a, const RedcliffCEmbArgs* ce, void* stream, int adam_idx) {
   if (!a || !ce) { rc_set_error("null step arguments"); return REDCLIFF_EINVAL; }
   if (a->flags & (RC_GRAD_ONLY | RC_REFRESH_SUPPORTS)) {
     rc_set_error("cEmbedder step: RC_GRAD_ONLY / RC_REFRESH_SUPPORTS are not supported");
@@ -572,6 +625,10 @@ int redcliff_cemb_train_step(const RedcliffStepArgs* a, const RedcliffCEmbArgs* 
   StepCtx c;
   if ((e = make_ctx(&sa, c, true))) return e;
   if (c.nrep == 0) return 0;
+  if (adam_idx >= 0) {
+    c.adt = c.ws + c.wo.adamt;
+    c.adi = adam_idx;
+  }
   CEmbCtx x;
   x.eh = ce->eh;
   x.po = rc_cemb_poff(c.d, ce->eh);
@@ -613,16 +670,25 @@ int redcliff_cemb_train_step(const RedcliffStepArgs* a, const RedcliffCEmbArgs* 
   return 0;
 }
 
+int redcliff_cemb_train_step(const RedcliffStepArgs* a, const RedcliffCEmbArgs* ce, void* stream) {
+  return cemb_train_step(a, ce, stream, -1);
+}
+
 int redcliff_cemb_train_steps(const RedcliffStepArgs* a, const RedcliffCEmbArgs* ce, int32_t nsteps, const int64_t* rows,
                               const int32_t* sizes, void* stream) {
   if (!a || !ce || nsteps < 0 || (nsteps > 0 && (!rows || !sizes))) { rc_set_error("cemb_train_steps: bad arguments"); return REDCLIFF_EINVAL; }
   RedcliffStepArgs s = *a;
+  // the Adam table as in redcliff_train_steps (one stream; the shared workspace laid out by the
+  // dims the step runs with)
+  RedcliffDims dd;
+  const int chunk = cemb_dims(&a->d, ce->eh, dd) == 0 ? adam_table_chunk(a, dd, nsteps) : 0;
   for (int32_t i = 0; i < nsteps; ++i) {
     s.row0 = rows[i];
     s.B = sizes[i];
     s.tA = a->tA + ((a->flags & RC_STEP_A) ? i : 0);
     s.tB = a->tB + ((a->flags & RC_STEP_B) ? i : 0);
-    const int e = redcliff_cemb_train_step(&s, ce, stream);
+    int e = adam_table_fill(a, dd, chunk, i, nsteps, stream);
+    if (!e) e = cemb_train_step(&s, ce, stream, chunk > 0 ? i % chunk : -1);
     if (e) return e;
   }
   return 0;

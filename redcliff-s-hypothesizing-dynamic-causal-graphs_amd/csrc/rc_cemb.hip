@@ -181,6 +181,10 @@ __global__ __launch_bounds__(RC_BLOCK) void k_cemb_bwd(StepCtx c, CEmbCtx e, int
   float* cw = e.ws + r * e.wss;
   const RedcliffReplicaHyper& hy = c.hyp[r];
   const int tid = threadIdx.x;
+  // fetched here, not ahead of the epilogue: there the two-way fetch left the kernel a 36-byte
+  // private segment (no access to it, but scratch set up per dispatch).  The scalar form: 7
+  // scalars live through the kernel, 75 vector registers and 6 waves as before (vector form: 81, 5)
+  const RcAdamScalars as = rc_adam_scalars<true>(c, 0, r);
   const bool gw_on = fac && (c.flags & (RC_LOSS_FORECAST | RC_LOSS_ADJ));
   const bool adj = fac && (c.flags & RC_LOSS_ADJ);
   __shared__ float dyv[512];  // dL/dw_raw[b][k], zero past B
@@ -253,7 +257,6 @@ __global__ __launch_bounds__(RC_BLOCK) void k_cemb_bwd(StepCtx c, CEmbCtx e, int
     gb1 = rc_block_sum(t, red);
   }
   // ---- epilogue: + the adjacency-L1 term through E and the group norms, then Adam
-  const RcAdamScalars as = rc_adam_scalars(hy.A, c.tA);
   const int u = u0 + uu;
   if (u < eh) {
 #pragma unroll

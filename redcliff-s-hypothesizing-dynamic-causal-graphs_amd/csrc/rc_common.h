@@ -61,8 +61,14 @@ struct WsOff {
   int64_t errw;   // [16] u32          device status words, never reset by a kernel: [0] counts the
                   //                   merged backward's hand-off waits that timed out (rc_wait_count);
                   //                   read and cleared by redcliff_device_status
+  int64_t adamt;  // [RC_ADAM_SMAX][2][8] Adam bias-correction table of a redcliff_train_steps chunk (k_adam_table):
+                  //                   entry (step i of the chunk, group A / B) = RcAdamScalars + one pad float
   int64_t total;
 };
+
+// Adam table (WsOff.adamt): steps per chunk and floats per entry (7 scalars, padded to 32 bytes)
+#define RC_ADAM_SMAX 256
+#define RC_ADAM_ENTRY 8
 
 __host__ __device__ inline int rc_lmax(const RedcliffDims& d) { return d.L > d.F ? d.L : d.F; }
 __host__ __device__ inline int rc_ls(const RedcliffDims& d) { return d.L < d.F ? d.L : d.F; }
@@ -212,6 +218,10 @@ inline WsOff rc_ws_off(const RedcliffDims& d, int64_t* ext = nullptr, int* next 
   put(o.edr, B * K);
   put(o.cosb, 2 * B);
   put(o.errw, 16);
+  // the Adam table follows the listed regions (with its own guard band) and is not one of them:
+  // callers index the region list redcliff_workspace_regions reports by position
+  o.adamt = x;
+  x = rc_align64(x + (int64_t)RC_ADAM_SMAX * 2 * RC_ADAM_ENTRY + G);
 #ifdef RC_TRACE
   x += RC_TRACE_FLOATS;  // phase-timing slots at the end of the workspace (trace builds only)
 #endif
@@ -354,6 +364,11 @@ struct StepCtx {
   const float* cE;
   float* cdE;
   int64_t cwss;
+  // Adam table of the redcliff_train_steps chunk this step belongs to (replica 0's WsOff.adamt,
+  // replica stride wss) and the step's index in the chunk; null: the kernels compute the scalars
+  // themselves (redcliff_train_step called directly, the data-parallel update)
+  const float* adt;
+  int adi;
 };
 
 __host__ __device__ inline int rc_rep(const StepCtx& c, int i) { return c.rident ? i : (int)c.rmap[i]; }
@@ -678,6 +693,40 @@ __device__ inline RcAdamScalars rc_adam_scalars(const RedcliffAdamHyper& h, int 
   s.omb2 = h.one_minus_beta2_f;
   return s;
 }
+// The scalars of this step for group 0 = A (embedder) / 1 = B (factors) of replica r: the entry
+// k_adam_table stored for the redcliff_train_steps chunk (the same function's values, evaluated
+// once per call instead of by every workgroup: two inlined double-double pow are ~480 dependent
+// vector instructions), or computed here when the step carries no table.  The entry is fetched
+// with per-lane loads of the one address (a broadcast; the values sit in vector registers, as
+// the computed ones did); RC_ADAM_TABLE_VLOAD=0 fetches it with ONE uniform scalar load through
+// the constant address space instead (the table was written by an earlier launch and nothing in
+// this one stores to it), which measured 0.2 us per D4IC step slower.  SLOAD = true
+// picks the scalar form for one call site (k_cemb_bwd, where the vector form costs a wave of occupancy).
+#ifndef RC_ADAM_TABLE_VLOAD
+#define RC_ADAM_TABLE_VLOAD 1
+#endif
+typedef float f32x8 __attribute__((ext_vector_type(8)));
+template <bool SLOAD = !RC_ADAM_TABLE_VLOAD>
+__device__ __forceinline__ RcAdamScalars rc_adam_scalars(const StepCtx& c, int group, int r) {
+  if (c.adt) {
+    const float* e = c.adt + (int64_t)r * c.wss + (2 * c.adi + group) * RC_ADAM_ENTRY;
+    RcAdamScalars s;
+    if constexpr (!SLOAD) {
+      auto ld = [e](int i) {
+        return __uint_as_float(__hip_atomic_load(reinterpret_cast<unsigned*>(const_cast<float*>(e)) + i, __ATOMIC_RELAXED,
+                                                 __HIP_MEMORY_SCOPE_WORKGROUP));
+      };
+      s.neg_step = ld(0); s.bc2s = ld(1); s.eps = ld(2); s.wd = ld(3); s.b2 = ld(4); s.omb1 = ld(5); s.omb2 = ld(6);
+    } else {
+      typedef const f32x8 __attribute__((address_space(4))) * CEntry;
+      const f32x8 v = *(CEntry)(uintptr_t)e;
+      s.neg_step = v[0]; s.bc2s = v[1]; s.eps = v[2]; s.wd = v[3]; s.b2 = v[4]; s.omb1 = v[5]; s.omb2 = v[6];
+    }
+    return s;
+  }
+  const RedcliffReplicaHyper& hy = c.hyp[r];
+  return rc_adam_scalars(group ? hy.B : hy.A, group ? c.tB : c.tA);
+}
 
 // torch.optim.Adam (_single_tensor_adam, coupled L2 weight decay) for one element:
 //   g += wd*p; m.lerp_(g, 1-b1); v.mul_(b2).addcmul_(g, g, 1-b2);
@@ -749,6 +798,9 @@ inline int rc_lds_optin(Kern k, size_t bytes, const char* what) {
 // stop (optional): an event the launch itself completes (hipExtLaunchKernel), so a second stream can
 // wait for this kernel without an event-record packet between it and the next kernel of `s`
 int rc_launch_forward(const StepCtx& c, hipStream_t s, bool with_emb, bool with_fac, hipEvent_t stop = nullptr);
+// the Adam table of one chunk of n <= RC_ADAM_SMAX steps, for all R replicas (rc_aux.hip k_adam_table)
+int rc_launch_adam_table(const RedcliffReplicaHyper* hyp, int R, int n, int tA0, int incA, int tB0, int incB, float* tab,
+                         int64_t wss, hipStream_t s);
 // fills StepCtx::mg from c.d and c.B (every StepCtx builder calls it last)
 void rc_ctx_magics(StepCtx& c);
 int rc_launch_fac_fwd(const StepCtx& c, hipStream_t s);

@@ -1247,7 +1247,7 @@ __global__ __launch_bounds__(RC_BLOCK) void k_dp_update(StepCtx c, int64_t nE, i
   const int p = c.d.p, pp = p * p;
   if (bx == 0) {
     if (!(c.flags & RC_STEP_A)) return;
-    const RcAdamScalars s = rc_adam_scalars(hy.A, c.tA);
+    const RcAdamScalars s = rc_adam_scalars(c, 0, r);
     float* P = c.emb + r * c.es;
     float* M = c.embM + r * c.es;
     float* V = c.embV + r * c.es;
@@ -1266,7 +1266,7 @@ __global__ __launch_bounds__(RC_BLOCK) void k_dp_update(StepCtx c, int64_t nE, i
     return;
   }
   const bool emb = bx <= nbE;
-  const RcAdamScalars s = rc_adam_scalars(emb ? hy.A : hy.B, emb ? c.tA : c.tB);
+  const RcAdamScalars s = rc_adam_scalars(c, emb ? 0 : 1, r);
   const int64_t st = emb ? c.es : c.fs, n = emb ? nE : nF;
   float* P = (emb ? c.emb : c.fac) + r * st;
   float* M = (emb ? c.embM : c.facM) + r * st;
@@ -1391,7 +1391,7 @@ __device__ __forceinline__ void emb_final_wg(const StepCtx& c, int wx, int wy, i
   float* V = c.embV + r * c.es;
   float* ws = c.ws + r * c.wss;
   const bool stepA = c.flags & RC_STEP_A;
-  const RcAdamScalars as = rc_adam_scalars(c.hyp[r].A, c.tA);
+  const RcAdamScalars as = rc_adam_scalars(c, 0, r);
   const int nFH = n * F * H, nfc = K * M1 + K + M1, nf1 = M1 * p * H;
   const int total = nFH + nfc + 2 * F + nf1;
   // c.defer == 2: the node blocks' window-block partials are summed here (no combine launch);
@@ -1841,7 +1841,7 @@ __global__ __launch_bounds__(RC_BLOCK) void k_emb_tail(StepCtx c) {
   float* Mm = c.embM + r * c.es;
   float* V = c.embV + r * c.es;
   const bool adam = !(c.flags & RC_GRAD_ONLY);
-  const RcAdamScalars as = rc_adam_scalars(c.hyp[r].A, c.tA);
+  const RcAdamScalars as = rc_adam_scalars(c, 0, r);
   const TailRoles tg = rc_tail_roles(d);
   RC_WG_MARK(c.ws, c.wo.total, RC_KID_EMB_FINAL, 0);
   int w = blockIdx.x - 1;

@@ -401,7 +401,7 @@ __device__ __forceinline__ void fac_bwd_wg(const StepCtx& c, int nUl, int nQ, in
   const int tbx = (kj == 0 && uc == 1 && qc == 0 && role == RC_FB_ALL) ? 0 : 1;
   (void)tbx;
   RC_PHASE(c.ws, c.wo.total, tbx, 19);
-  const RcAdamScalars as = rc_adam_scalars(hy.B, c.tB);
+  const RcAdamScalars as = rc_adam_scalars(c, 1, r);
   // ---- part 3: over window tiles of FB_BT (one tile when B <= 128; the first is already staged)
   const int uu = tid & 15, part = tid >> 4;  // 3a: 16 slices of the batch per hidden unit
   float dW1u = 0.f, db0u = 0.f, db1 = 0.f;

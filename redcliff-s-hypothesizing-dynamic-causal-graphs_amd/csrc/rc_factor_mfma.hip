@@ -458,7 +458,7 @@ __global__ __launch_bounds__(NT) void k_fac_mix(StepCtx c, int xcd) {
   __syncthreads();
   RC_PHASE(c.ws, c.wo.total, blockIdx.x, 22);
   // ---- output layer / hidden bias gradients + Adam: 32 units x 8 batch slices per pass
-  const RcAdamScalars as = rc_adam_scalars(hy.B, c.tB);
+  const RcAdamScalars as = rc_adam_scalars(c, 1, r);
   const float* aw = ws + c.wo.a + (int64_t)kj * d.Bmax * h;
   const float* W1 = ws + c.wo.w1 + (int64_t)kj * h;  // pre-update snapshot written by the forward
   float db1v[NV];
@@ -597,7 +597,7 @@ __global__ __launch_bounds__(RC_BLOCK) __attribute__((amdgpu_waves_per_eu(NBW ==
   const int cbw = cb0 + net, kin = cbw < NB;
   const int kj = kin ? cbw / nUB : 0, ub0 = kin ? (cbw - kj * nUB) * 32 : 0;
   const bool adj_grad = (c.flags & RC_LOSS_ADJ) && ((c.flags & RC_STEP_B) || (c.flags & RC_STEP_A));
-  const RcAdamScalars as = rc_adam_scalars(hy.B, c.tB);
+  const RcAdamScalars as = rc_adam_scalars(c, 1, r);
   const bool adam = !(c.flags & RC_GRAD_ONLY);
   float* W0 = P + c.fo.W0 + (int64_t)(kin ? kj : 0) * h * Q;
   float* M0 = PM + c.fo.W0 + (int64_t)(kin ? kj : 0) * h * Q;
@@ -1050,7 +1050,7 @@ __global__ RC_S16_BWD_BOUNDS void k_fac_bwd_s16(StepCtx c, int bpw, int xcd) {
   float* GF = c.gF + r * c.fs;
   const float* ws = c.ws + r * c.wss;
   const RedcliffReplicaHyper& hy = c.hyp[r];
-  const RcAdamScalars as = rc_adam_scalars(hy.B, c.tB);
+  const RcAdamScalars as = rc_adam_scalars(c, 1, r);
   const bool adam = !(c.flags & RC_GRAD_ONLY);
   const bool adj_grad = (c.flags & RC_LOSS_ADJ) && ((c.flags & RC_STEP_B) || (c.flags & RC_STEP_A));
   // the Adam moments are read only when they exist (RC_GRAD_ONLY steps may run without them)

@@ -34,7 +34,7 @@ WS_REGIONS = ("T", "R", "f1", "w", "a", "y", "G", "G0", "w1", "gq", "ebp", "ecnt
 
 EXPORTED = ("redcliff_abi_version", "redcliff_last_error", "redcliff_workspace_bytes", "redcliff_emb_param_count",
             "redcliff_fac_param_count", "redcliff_bn_batch_stats", "redcliff_dgcnn_supports", "redcliff_train_step",
-            "redcliff_train_steps", "redcliff_workspace_layout", "redcliff_factor_forward",
+            "redcliff_train_steps", "redcliff_adam_table_layout", "redcliff_workspace_layout", "redcliff_factor_forward",
             "redcliff_factor_forward_workspace_floats", "redcliff_step_predictions", "redcliff_gc_norms",
             "redcliff_prox", "redcliff_kernel_timing", "redcliff_kernel_times", "redcliff_adam_apply", "redcliff_dp_update", "redcliff_gemm",
             "redcliff_gc_progress", "redcliff_gc_progress_grouped", "redcliff_debug_guard_bands", "redcliff_workspace_regions",
@@ -204,6 +204,7 @@ def lib():
     L.redcliff_dgcnn_supports.argtypes = [ctypes.POINTER(Dims), _vp, _i64, _vp, _vp]
     L.redcliff_train_step.argtypes = [ctypes.POINTER(StepArgs), _vp]
     L.redcliff_train_steps.argtypes = [ctypes.POINTER(StepArgs), ctypes.c_int32, _vp, _vp, ctypes.c_int32, _vp]
+    L.redcliff_adam_table_layout.argtypes = [ctypes.POINTER(Dims), ctypes.POINTER(_i64)]
     L.redcliff_workspace_layout.argtypes = [ctypes.POINTER(Dims), ctypes.POINTER(_i64), ctypes.c_int32]
     L.redcliff_factor_forward.argtypes = [ctypes.POINTER(Dims), ctypes.c_int32, _vp, _i64, _vp, _i64, _vp, _i64, _vp,
                                           _i64, _vp]
@@ -327,6 +328,14 @@ def workspace_layout(dims):
     if n < 0:
         check(n, "workspace_layout")
     return dict(zip(WS_REGIONS, [int(v) for v in out]))
+
+
+def adam_table_layout(dims):
+    """(offset in a replica's workspace slice, steps per chunk in effect, floats per entry) of the
+    Adam table redcliff_train_steps fills (include/redcliff_hip.h)."""
+    out = (_i64 * 3)()
+    check(lib().redcliff_adam_table_layout(ctypes.byref(dims), out), "adam_table_layout")
+    return int(out[0]), int(out[1]), int(out[2])
 
 
 def status_view(ws, ws_off, R):

@@ -3,9 +3,11 @@
 Compiles every csrc/*.hip (or the files named on the command line) to gfx950 assembly with
 build.py's flags and prints, per kernel: code bytes, VGPRs, occupancy, scratch bytes, spilled
 scalars, the number of lane moves (v_readlane_b32 / v_writelane_b32: scalar spill traffic),
-the number of matrix-core instructions, and how many of those directly follow a full LDS wait
+the number of matrix-core instructions, how many of those directly follow a full LDS wait
 (s_waitcnt lgkmcnt(0) as the previous instruction: an MFMA that waits for its own operands'
-round trip).  The assembly is read for these quantities only.
+round trip), and the number of double-precision vector instructions (v_*_f64*: the chip has no
+scalar double arithmetic, so uniform double math such as the Adam bias corrections' pow runs on
+the vector unit; static count, taken or not).  The assembly is read for these quantities only.
 
   python scripts/chain_report.py [--filter SUBSTR] [--csrc DIR] [--keep DIR] [file.hip ...]
 """
@@ -69,7 +71,7 @@ def parse(path):
             vgprs[name] = int(m.group(1))
         m = _LABEL.match(raw)
         if m and not m.group(1).startswith(".L"):
-            cur = {"lane": 0, "mfma": 0, "mfma_wait": 0}
+            cur = {"lane": 0, "mfma": 0, "mfma_wait": 0, "f64": 0}
             kernels[m.group(1)] = cur
             prev = ""
             continue
@@ -90,6 +92,8 @@ def parse(path):
             cur["mfma"] += 1
             if _FULL_LDS_WAIT.match(prev):
                 cur["mfma_wait"] += 1
+        elif op.startswith("v_") and "_f64" in op:
+            cur["f64"] += 1
         prev = line
     out = {}
     for sym, k in kernels.items():
@@ -108,8 +112,8 @@ def main():
     ap.add_argument("--keep", default="", help="write the assembly files into this directory")
     a = ap.parse_args()
     files = a.files or sorted(os.path.join(a.csrc, f) for f in os.listdir(a.csrc) if f.endswith(".hip"))
-    print("%-58s %8s %5s %3s %7s %6s %6s %5s %9s" %
-          ("kernel", "bytes", "vgpr", "occ", "scratch", "sspill", "lanemv", "mfma", "mfma@wait"))
+    print("%-58s %8s %5s %3s %7s %6s %6s %5s %9s %5s" %
+          ("kernel", "bytes", "vgpr", "occ", "scratch", "sspill", "lanemv", "mfma", "mfma@wait", "f64"))
     with tempfile.TemporaryDirectory(prefix="rc_asm_") as tmp:
         if a.keep:
             os.makedirs(a.keep, exist_ok=True)
@@ -125,9 +129,9 @@ def main():
             if rows:
                 print("# %s" % os.path.basename(src))
             for nm, k in rows:
-                print("%-58s %8d %5d %3d %7d %6d %6d %5d %9d" %
+                print("%-58s %8d %5d %3d %7d %6d %6d %5d %9d %5d" %
                       (nm[:58], k["code"], k.get("vgpr", -1), k.get("occ", -1), k.get("scratch", -1), k["spill"],
-                       k["lane"], k["mfma"], k["mfma_wait"]))
+                       k["lane"], k["mfma"], k["mfma_wait"], k["f64"]))
 
 
 if __name__ == "__main__":
