@@ -797,6 +797,60 @@ int redcliff_dcsfa_supported(int32_t D, int32_t H, int32_t K, int32_t ns, int32_
 int64_t redcliff_dcsfa_ws_floats(int32_t H, int32_t K, int32_t B);
 int redcliff_dcsfa_run(const RedcliffDcsfaArgs* a, void* stream);
 
+/* ---- directed-spectrum features (general_utils/directed_spectrum.py, pairwise, and
+ * general_utils/time_series.py make_high_level_signal_features) ----
+ * Purely additive entries: REDCLIFF_ABI_VERSION stays 10, no kernel id, no existing entry or layout changes.
+ *
+ * For each of N windows X[n][T][p] (float32 or float64; x_wstride elements between windows, x_tstride between
+ * time steps, channels contiguous) the features the reference's data sets build one window at a time:
+ *   Welch spectra of the nseg = (T - noverlap) / (nperseg - noverlap) segments (detrend "constant", periodic
+ *   Hann window, two-sided DFT of length F = nperseg, density scaling 1 / (fs sum w^2)), in double;
+ *   per channel pair a < b the 2x2 CPSD [[c_aa, c_ab], [c_ba, c_bb]], c_ab = mean_s conj(X_b) X_a, rounded once
+ *   to complex64 for float32 input;
+ *   the singular branch: taken by rule when nseg < 2, else when the closed-form condition number of the
+ *   Hermitian 2x2 (ratio of its singular values, in the input's precision) exceeds 1 / eps at any frequency of
+ *   the pair; it adds spacing(max |c|) * 100 of THAT pair and window to the diagonal and continues in double;
+ *   the Wilson factorisation (at most max_iter iterations, the reference's two-stage relative-change test with
+ *   tol), H = psi A0^-1, Sigma = A0 A0^T, ds[a][b] = |H_ba|^2 (S_aa - S_ab^2 / S_bb), ds[b][a] likewise;
+ *   the one-sided fold (bins 1 .. F/2 - 1 doubled, the Nyquist bin only for odd F), times the bin frequency
+ *   k / (F (1 / fs)), cropped to the bins [i1, i2) = searchsorted(f, [min_freq, max_freq]); n_f = i2 - i1.
+ * out row n (float32, out_rstride floats between rows, only the row's own columns are written):
+ *   REDCLIFF_DIRSPEC_VANILLA    [p][p][n_f]            column (i p + j) n_f + k
+ *   REDCLIFF_DIRSPEC_FLATTENED  [p][n_f][2p - 1]       flatten_directed_spectrum_features, row-major
+ * power (optional, may be NULL): [N][p (p + 1) / 2][n_f] doubles, |one-sided CPSD| of channel pairs
+ *   (r, c <= r) at index r (r + 1) / 2 + c, times the bin frequency.
+ * status / iters: [N][p (p - 1) / 2] int32 per (window, pair in the order (0,1), (0,2), ..., (p-2,p-1)):
+ *   REDCLIFF_DIRSPEC_CONVERGED, _MAXITER (the features are those of the last iteration, as in the reference) or
+ *   _PIVOT (a non-positive Cholesky pivot: the pair's features are NaN), and the iterations run.
+ * A window holding a NaN gives a NaN row (and NaN power), runs no factorisation and reports CONVERGED, 0.
+ * ws: redcliff_dirspec_ws_bytes(...) bytes, 16-byte aligned (the spectra and the NaN flags).
+ * Limits: nperseg <= 256, p <= 1024, T >= nperseg > noverlap >= 0; outside them REDCLIFF_ELIMIT /
+ * REDCLIFF_EINVAL and redcliff_dirspec_supported returns 0.  All checks precede any HIP call.
+ * Stream-ordered, no host synchronisation, no atomics: the same arguments give the same bits, and a window's
+ * row does not depend on the other windows of the call. */
+#define REDCLIFF_DIRSPEC_F32 0
+#define REDCLIFF_DIRSPEC_F64 1
+#define REDCLIFF_DIRSPEC_VANILLA 0
+#define REDCLIFF_DIRSPEC_FLATTENED 1
+#define REDCLIFF_DIRSPEC_CONVERGED 0
+#define REDCLIFF_DIRSPEC_MAXITER 1
+#define REDCLIFF_DIRSPEC_PIVOT 2
+typedef struct RedcliffDirspecArgs {
+  int32_t N, T, p, nperseg, noverlap, max_iter;
+  int32_t dtype, layout;
+  double fs, min_freq, max_freq, tol;
+  const void* X; int64_t x_wstride, x_tstride;
+  float* out; int64_t out_rstride;
+  double* power;
+  void* ws; size_t ws_bytes;
+  int32_t* status; int32_t* iters;
+} RedcliffDirspecArgs;
+int redcliff_dirspec_supported(int32_t T, int32_t p, int32_t nperseg, int32_t noverlap);
+/* n_f for these bins (negative: an error code) */
+int redcliff_dirspec_nfreq(int32_t nperseg, double fs, double min_freq, double max_freq);
+size_t redcliff_dirspec_ws_bytes(int32_t N, int32_t T, int32_t p, int32_t nperseg, int32_t noverlap);
+int redcliff_dirspec_run(const RedcliffDirspecArgs* a, void* stream);
+
 /* Per-kernel HIP-event timing for benchmarking: redcliff_kernel_timing(1) brackets every
  * kernel launched by redcliff_train_step with events on its stream; redcliff_kernel_times()
  * synchronises them and returns per-kernel totals (ids 0..11: supports, emb_fwd, fac_fwd,

@@ -17,10 +17,18 @@ from .clstm_fm import cLSTM_FM, fit_lstm_baselines
 from .navar import NAVAR, fit_navar_baselines
 from .navar_lstm import NAVARLSTM, fit_navar_lstm_baselines
 from .dcsfa_nmf import DcsfaFitPack, DcsfaNmf, FullDCSFAModel, FullDCSFAModel_GCv2, NmfBase, fit_dcsfa_baselines
+from .directed_spectrum import (DEFAULT_CSD_PARAMS, directed_spectrum_features, flatten_directed_spectrum_features,
+                                get_directed_spectrum, make_high_level_signal_features)
+from .data import (load_normalized_DREAM4_data_train_test_split_as_matrices,
+                   load_normalized_lfp_data_train_test_split_as_matrices)
 
 __all__ = ["MLP", "cMLP", "DGCNN", "DGCNN_Model", "DGCNN_Embedder", "cEmbedder", "MLPClassifierForSingleObjective",
            "MLPClassifierForMultipleObjectives", "REDCLIFF_S_CMLP", "REDCLIFF_S_CMLP_withStateSmoothing", "ReplicaPack",
            "PerReplica", "fit_packs", "grid_packs", "shard_grid", "DataParallelFit",
            "score_recordings", "cMLP_FM", "fit_baselines", "LSTM", "cLSTM", "cLSTM_FM", "fit_lstm_baselines",
            "NAVAR", "fit_navar_baselines", "NAVARLSTM", "fit_navar_lstm_baselines", "fit_dgcnn_baselines",
-           "NmfBase", "DcsfaNmf", "FullDCSFAModel", "FullDCSFAModel_GCv2", "DcsfaFitPack", "fit_dcsfa_baselines"]
+           "NmfBase", "DcsfaNmf", "FullDCSFAModel", "FullDCSFAModel_GCv2", "DcsfaFitPack", "fit_dcsfa_baselines",
+           "DEFAULT_CSD_PARAMS", "get_directed_spectrum", "make_high_level_signal_features",
+           "flatten_directed_spectrum_features", "directed_spectrum_features",
+           "load_normalized_DREAM4_data_train_test_split_as_matrices",
+           "load_normalized_lfp_data_train_test_split_as_matrices"]

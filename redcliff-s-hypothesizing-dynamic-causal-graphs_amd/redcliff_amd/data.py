@@ -334,3 +334,68 @@ def load_normalized_lfp_data_train_test_split(data_root_path, batch_size, shuffl
     tp, vp = _split_dirs(data_root_path, train_portion, lambda x: "subset_" in x)
     return tuple(NormalizedRecordingDirectory(p, "lfp", shuffle, shuffle_seed, grid_search, average_region_map)
                  .batches(batch_size, device) for p in (tp, vp))
+
+
+# --------------------------------------------------------------------------- feature-matrix loaders
+def _label_matrix(labels):
+    """The ``*_as_matrices`` loaders' label matrix: squeezed 1-D labels stacked, a zero column for scalar labels
+    (the reference leaves it unfilled); other label shapes fail there as well."""
+    ys = [np.squeeze(np.asarray(y, dtype=np.float32)) for y in labels]
+    if ys and ys[0].ndim < 1:
+        return np.zeros((len(ys), 1), np.float32)
+    if any(y.ndim != 1 for y in ys):
+        raise ValueError("the *_as_matrices loaders need one label vector per recording")
+    return np.stack(ys) if ys else np.zeros((0, 0), np.float32)
+
+
+def _as_matrices(ds, signal_format, max_num_features_per_series, dirspec_params, device=None):
+    """(X, Y) of one data set in ``signal_format``, every item at once.  The directed-spectrum formats take the
+    first max_num_features_per_series steps of every normalised recording through
+    directed_spectrum.directed_spectrum_features; the normalised values stay float64 on the way there, as the
+    reference's items do (its float32 recording minus its float64 statistics is float64)."""
+    Y = _label_matrix([ds.labels[i] for i in ds.data])
+    if "directed_spectrum" in signal_format:
+        from .directed_spectrum import directed_spectrum_features
+        if dirspec_params is None or not dirspec_params.get("directed_spectrum", False):
+            raise ValueError("signal_format %r needs dirspec_params with directed_spectrum=True" % signal_format)
+        Xn, _ = ds.materialize(dtype=torch.float64)
+        Xn = Xn[:, :max_num_features_per_series, :]
+        layout = "vanilla" if "vanilla" in signal_format else "flattened"
+        X = directed_spectrum_features(Xn, dirspec_params["fs"], dirspec_params["min_freq"], dirspec_params["max_freq"],
+                                       dirspec_params["csd_params"], layout=layout, device=device)
+        X = X.cpu().numpy() if torch.is_tensor(X) else X
+    elif "power_features" in signal_format:
+        raise NotImplementedError("power_features")
+    elif "flattened" in signal_format:
+        assert max_num_features_per_series is not None and max_num_features_per_series > 0
+        Xn, _ = ds.materialize()
+        X = Xn[:, :max_num_features_per_series, :].reshape(Xn.shape[0], -1).numpy()
+    else:
+        raise ValueError("the *_as_matrices loaders return one feature vector per recording: signal_format %r" % signal_format)
+    return X, Y
+
+
+def load_normalized_DREAM4_data_train_test_split_as_matrices(data_root_path, signal_format="original flattened", shuffle=True,
+                                                             shuffle_seed=0, max_num_features_per_series=25, train_portion=0.8,
+                                                             dirspec_params=None, grid_search=True, device=None):
+    """dream4_datasets.py:192-270 -> X_train, y_train, X_val, y_val (numpy float32)."""
+    tp, vp = _split_dirs(data_root_path, train_portion, lambda x: "subset_" in x)
+    out = []
+    for path in (tp, vp):
+        ds = NormalizedRecordingDirectory(path, "dream4", shuffle, shuffle_seed, grid_search)
+        out.extend(_as_matrices(ds, signal_format, max_num_features_per_series, dirspec_params, device))
+    return tuple(out)
+
+
+def load_normalized_lfp_data_train_test_split_as_matrices(data_root_path, signal_format="original flattened", shuffle=True,
+                                                          shuffle_seed=0, max_num_features_per_series=25, train_portion=0.8,
+                                                          dirspec_params=None, grid_search=True, average_region_map=None,
+                                                          device=None):
+    """local_field_potential_datasets.py:222-end -> X_train, y_train, X_val, y_val (numpy float32); the file
+    filters of load_normalized_lfp_data_train_test_split apply."""
+    tp, vp = _split_dirs(data_root_path, train_portion, lambda x: "subset_" in x)
+    out = []
+    for path in (tp, vp):
+        ds = NormalizedRecordingDirectory(path, "lfp", shuffle, shuffle_seed, grid_search, average_region_map)
+        out.extend(_as_matrices(ds, signal_format, max_num_features_per_series, dirspec_params, device))
+    return tuple(out)
