@@ -308,11 +308,13 @@ struct CEmbCtx {
 
 // Everything a step kernel needs, passed by value.
 // StepCtx::mg slots: F, p, p F, n F, K, M1, H, L, B, n p F, p H, and per fc1 slice width of the
-// embedder forward (cw channels: the regular width cs and the last slice's): cw F, n cw F, cw H
+// embedder forward (cw channels: the regular width cs and the last slice's): cw F, n cw F, cw H;
+// then the divisors of the factor kernels' slab staging: Q = p L (a window's slab, a W0 row) and the
+// hidden chunks per network
 enum {
   RC_MG_F, RC_MG_P, RC_MG_PF, RC_MG_NF, RC_MG_K, RC_MG_M1, RC_MG_H, RC_MG_L, RC_MG_B, RC_MG_NPF, RC_MG_PH,
   RC_MG_CS, RC_MG_CSF, RC_MG_NCSF, RC_MG_CSH, RC_MG_LS, RC_MG_LSF, RC_MG_NLSF, RC_MG_LSH, RC_MG_NCH, RC_MG_ENBW,
-  RC_MG_ZS, RC_MG_N
+  RC_MG_ZS, RC_MG_Q, RC_MG_NU, RC_MG_N
 };
 
 struct StepCtx {
@@ -598,6 +600,129 @@ __device__ inline void rc_stage_all(S&&... s) {
     (s.load(r), ...);
     (s.store(r), ...);
   }
+}
+
+// A segment whose ld(e) is valid for every e in [0, N): the loads carry no per-lane guard (a guarded
+// load is an exec-mask branch per element).  Whole groups of RC_BLOCK elements past N are skipped
+// by a uniform (scalar) test, the lanes past N of the last group load element N - 1 and store nothing.
+template <int U, class Ld, class St>
+struct RcSegC {
+  int N;
+  Ld ld;
+  St st;
+  float v[U];
+  __device__ inline bool active(int r) const { return r * U * RC_BLOCK < N; }
+  __device__ inline void load(int r) {
+#pragma unroll
+    for (int u = 0; u < U; ++u) {
+      const int e0 = (r * U + u) * RC_BLOCK;
+      if (e0 < N) v[u] = ld(min(e0 + (int)threadIdx.x, N - 1));
+    }
+  }
+  __device__ inline void store(int r) {
+#pragma unroll
+    for (int u = 0; u < U; ++u) {
+      const int e0 = (r * U + u) * RC_BLOCK, e = e0 + (int)threadIdx.x;
+      if (e0 < N && e < N) st(e, v[u]);
+    }
+  }
+};
+template <int U, class Ld, class St>
+__device__ inline RcSegC<U, Ld, St> rc_segc(int N, Ld ld, St st) {
+  return RcSegC<U, Ld, St>{N, ld, st};
+}
+
+// The lag windows of a tile of batch rows, as the factor kernels stage them: tile[b][q], q = ch L + t,
+// of X[(row + b) T p + (Lmax - L + t) p + ch].  One row's window is ONE contiguous slab of Q = L p
+// floats at base + b T p, so the slab form enumerates elements in memory order, e -> (b, s = t p + ch),
+// loads base[b T p + s] (lane-contiguous dwords; a slab is 4-byte aligned in general) and stores at
+// column (s mod p) L + s div p: one host-multiplier division per side, 32-bit offsets from the one
+// 64-bit pointer of the workgroup (base: the replica, row0, the tile's first row and Lmax - L folded
+// in; the launchers check Bmax T p < 2^30).  N = nb Q: the columns [Q, padto) of the nb rows are
+// zero-filled by LDS stores alone.  General form (a column tile that is not the whole slab: q0 > 0
+// or Q above the tile width 1 << TWL): element e = b << TWL | qq loads column q0 + qq where it is
+// below Q (a clamped address and a select, no branch) and zero elsewhere.
+struct RcWin {
+  const float* base;
+  int Tp, p, L, Q;
+  unsigned mQ, mp, mL;  // RcDiv32 multipliers of Q, p, L (StepCtx::mg)
+};
+__device__ __forceinline__ RcWin rc_win(const StepCtx& c, const float* X, int b0) {
+  const RedcliffDims& d = c.d;
+  return RcWin{X + ((c.row0 + b0) * d.T + (c.Lmax - d.L)) * d.p, d.T * d.p, d.p, d.L, d.p * d.L,
+               c.mg[RC_MG_Q], c.mg[RC_MG_P], c.mg[RC_MG_L]};
+}
+template <int U, int TWL>
+struct RcWinSeg {
+  RcWin w;
+  int N, nb, q0, stride, padto;
+  bool slab;
+  float* tile;
+  float v[U];
+  __device__ __forceinline__ bool active(int r) const { return r * U * RC_BLOCK < N; }
+  __device__ __forceinline__ void load(int r) {
+    if (slab) {
+      const RcDiv32 dQ(w.Q, w.mQ);
+#pragma unroll
+      for (int u = 0; u < U; ++u) {
+        const int e0 = (r * U + u) * RC_BLOCK;
+        if (e0 < N) {
+          const int e = min(e0 + (int)threadIdx.x, N - 1), b = dQ.div(e);
+          v[u] = w.base[(unsigned)(e + b * (w.Tp - w.Q))];
+        }
+      }
+    } else {
+      const RcDiv32 dL(w.L, w.mL);
+#pragma unroll
+      for (int u = 0; u < U; ++u) {
+        const int e0 = (r * U + u) * RC_BLOCK;
+        if (e0 < N) {
+          const int e = min(e0 + (int)threadIdx.x, N - 1), b = e >> TWL, q = q0 + (e & ((1 << TWL) - 1));
+          const bool in = q < w.Q;
+          const int qc = in ? q : 0, ch = dL.div(qc), t = qc - ch * w.L;
+          const float x = w.base[(unsigned)(b * w.Tp + t * w.p + ch)];
+          v[u] = in ? x : 0.f;
+        }
+      }
+    }
+  }
+  __device__ __forceinline__ void store(int r) {
+    if (slab) {
+      const RcDiv32 dQ(w.Q, w.mQ), dp(w.p, w.mp);
+#pragma unroll
+      for (int u = 0; u < U; ++u) {
+        const int e0 = (r * U + u) * RC_BLOCK, e = e0 + (int)threadIdx.x;
+        if (e0 < N && e < N) {
+          const int b = dQ.div(e), s = e - b * w.Q, t = dp.div(s), ch = s - t * w.p;
+          tile[b * stride + ch * w.L + t] = v[u];
+        }
+      }
+      const int pw = padto - w.Q;  // padding columns: 16, 32 or 64 lanes per row
+      if (r == 0 && pw > 0 && N > 0) {
+        const int sh = pw <= 16 ? 4 : (pw <= 32 ? 5 : 6), col = (int)threadIdx.x & ((1 << sh) - 1);
+        if (col < pw)
+          for (int b = (int)threadIdx.x >> sh; b < nb; b += RC_BLOCK >> sh) tile[b * stride + w.Q + col] = 0.f;
+      }
+    } else {
+#pragma unroll
+      for (int u = 0; u < U; ++u) {
+        const int e0 = (r * U + u) * RC_BLOCK, e = e0 + (int)threadIdx.x;
+        if (e0 < N && e < N) tile[(e >> TWL) * stride + (e & ((1 << TWL) - 1))] = v[u];
+      }
+    }
+  }
+};
+// rows [0, nb) of the tile at `tile` (row stride `stride`); slab: the whole window (q0 == 0, Q columns,
+// zeros up to padto), else columns [q0, q0 + (1 << TWL)).  nb == 0: an empty segment.
+template <int U, int TWL>
+__device__ __forceinline__ RcWinSeg<U, TWL> rc_win_seg(const RcWin w, bool slab, int nb, int q0, float* tile, int stride, int padto) {
+  RcWinSeg<U, TWL> s;
+  s.w = w;
+  s.N = slab ? nb * w.Q : nb << TWL;
+  s.nb = nb; s.q0 = q0; s.stride = stride; s.padto = padto;
+  s.slab = slab;
+  s.tile = tile;
+  return s;
 }
 
 // Kernels of the embedder chain (the critical path when the factor chain runs concurrently on

@@ -2048,6 +2048,7 @@ int rc_bwd_merged_grid(const StepCtx& c) {
 int rc_launch_bwd_merged(const StepCtx& c, hipStream_t s) {
   const RedcliffDims& d = c.d;
   if (c.defer != 1 || (c.flags & RC_VALUES)) { rc_set_error("merged backward: needs defer == 1 and no values"); return REDCLIFF_EINVAL; }
+  if ((int64_t)c.d.Bmax * c.d.T * c.d.p >= (1ll << 30)) { rc_set_error("merged backward: Bmax*T*p < 2^30 required"); return REDCLIFF_ELIMIT; }
   const size_t le = rc_emb_bwd_lds(d, false), lf = sizeof(float) * (size_t)fac_bwd_lds_floats(d);
   const size_t lds = le > lf ? le : lf;
   if (lds > RC_LDS_MAX_FLOATS * sizeof(float)) { rc_set_error("merged backward: LDS budget exceeded"); return REDCLIFF_ELIMIT; }

@@ -22,13 +22,6 @@ namespace {
 // (a batch's reads past Q or nb stay inside the tiles' rows: no index clamp in these chains)
 static_assert(FB_QT % (4 * FB_KB) == 0 && FB_BT % (4 * FB_KB) == 0, "operand batches must tile the LDS tiles");
 
-template <class Div>
-__device__ inline float xwin(const StepCtx& c, const Div& dL, const float* X, int b, int q) {
-  const int L = c.d.L;
-  const int ch = dL.div(q), t = q - ch * L;
-  return X[((c.row0 + b) * c.d.T + (c.Lmax - L + t)) * c.d.p + ch];
-}
-
 // ------------------------------------------------------------------------------------------
 // K2b: mixing, forecast loss, adjacency L1, backward and Adam.  grid (K*p*nU*nQ, R):
 // workgroup (network kj, hidden chunk uc, dW0 column tile qc).  The cheap per-window work
@@ -87,7 +80,8 @@ __device__ __forceinline__ void fac_bwd_wg(const StepCtx& c, int nUl, int nQ, in
   const RedcliffReplicaHyper& hy = c.hyp[r];
   const int tid = threadIdx.x;
   const int B = c.B;
-  const RcDiv32 dL(d.L, c.mg[RC_MG_L]), dB(B, c.mg[RC_MG_B]);
+  const RcDiv32 dB(B, c.mg[RC_MG_B]), dQ(Q, c.mg[RC_MG_Q]);
+  const bool slab = Q <= FB_QT;  // one dW0 column tile (q0 == 0): a tile row is the window's whole slab
   const bool sig = d.use_sigmoid;
   const float ecc = d.sigmoid_ecc;
   const bool fgrad = (c.flags & RC_STEP_B) || (c.flags & RC_STEP_A);
@@ -97,6 +91,11 @@ __device__ __forceinline__ void fac_bwd_wg(const StepCtx& c, int nUl, int nQ, in
   const bool tgt = c.flags & (RC_LOSS_FORECAST | RC_VALUES);
   const int Ls = c.Ls;
   RC_WG_MARK(c.ws, c.wo.total, RC_KID_FAC_BWD, 0);
+  // trace builds: the update part's phases are recorded by the (network 0, chunk 1) workgroup, a
+  // non-lead one: 26 = its start, 27 = its one staging pass done
+  const int tbx = (kj == 0 && uc == 1 && qc == 0 && role == RC_FB_ALL) ? 0 : 1;
+  (void)tbx;
+  RC_PHASE(c.ws, c.wo.total, tbx, 26);
 
   float* ybuf = sm;                        // [Bmax][K]  per-factor predictions
   float* wrl = ybuf + d.Bmax * K;          // [Bmax][K]  raw embedder outputs
@@ -173,7 +172,13 @@ __device__ __forceinline__ void fac_bwd_wg(const StepCtx& c, int nUl, int nQ, in
   const float* aw = ws + c.wo.a + (int64_t)kj * d.Bmax * h;
   const float* W1snap = ws + c.wo.w1 + (int64_t)kj * h;  // pre-update snapshot written by the forward
   const int64_t ys_ = (int64_t)d.Bmax * K * p;
+  // the forecast targets X[row0 + b][Lmax][j]: 32-bit offsets from one pointer (Bmax T p < 2^30 by
+  // the launchers' check)
+  const int Tp = d.T * p;
+  const float* xtg = X + (c.row0 * d.T + c.Lmax) * p + j;
   const int nb0 = min(B, FB_BT);
+  const int nrowc = min(FAC_UC, h - u0);
+  const float* Wc0 = P + kjW0 + u0 * Q;
   // the dW0 / Adam operands (late: staged after the lead's publish)
   auto stage_update = [&](bool on) {
     rc_stage_all(
@@ -183,17 +188,20 @@ __device__ __forceinline__ void fac_bwd_wg(const StepCtx& c, int nUl, int nQ, in
           const int bb = e >> 4, uu = e & 15;
           return u0 + uu < h ? aw[(int64_t)bb * h + u0 + uu] : 0.f;
         }, [&](int e, float v) { awl[(e >> 4) * (FAC_UC + 1) + (e & 15)] = v; }),
-        rc_seg<4>(on && stepB && recompute ? FAC_UC * Q : 0, [&](int e) {
-          const int uu = e / Q, q = e - uu * Q;
-          return u0 + uu < h ? P[kjW0 + (u0 + uu) * Q + q] : 0.f;
-        }, [&](int e, float v) { Wc[(e / Q) * (FB_QT + 1) + e % Q] = v; }),
+        // the chunk's W0 rows below h: nrowc * Q contiguous floats (recompute: Q <= FB_QT)
+        rc_segc<4>(on && stepB && recompute ? nrowc * Q : 0, [&](int e) { return Wc0[(unsigned)e]; }, [&](int e, float v) {
+          const int uu = dQ.div(e);
+          Wc[uu * (FB_QT + 1) + e - uu * Q] = v;
+        }),
         rc_seg<1>(on && stepB && recompute ? FAC_UC : 0, [&](int e) {
           return u0 + e < h ? P[(int)c.fo.b0 + kj * h + u0 + e] : 0.f;
         }, [&](int e, float v) { bc0[e] = v; }),
-        rc_seg<32>(on && stepB ? nb0 * FB_QT : 0, [&](int e) {
-          const int bb = e >> 6, qq = e & 63;
-          return q0 + qq < Q ? xwin(c, dL, X, bb, q0 + qq) : 0.f;
-        }, [&](int e, float v) { Xs[(e >> 6) * (FB_QT + 1) + (e & 63)] = v; }));
+        rc_win_seg<32, 6>(rc_win(c, X, 0), slab, on && stepB ? nb0 : 0, q0, Xs, FB_QT + 1, FB_QT));
+    if (on && stepB && recompute)  // a partial chunk: the rows past h are zero
+      for (int e = nrowc * Q + tid; e < FAC_UC * Q; e += RC_BLOCK) {
+        const int uu = dQ.div(e);
+        Wc[uu * (FB_QT + 1) + e - uu * Q] = 0.f;
+      }
   };
   if (!split && role != RC_FB_RECORDS) stage_update(true);
   // The two partial sums come last and load every slot unconditionally (slots >= nU read slot 0
@@ -201,7 +209,7 @@ __device__ __forceinline__ void fac_bwd_wg(const StepCtx& c, int nUl, int nQ, in
   // loads before the next element's are issued -- one memory round per element otherwise.
   rc_stage_all(
       rc_seg<8>(B * K, [&](int e) { return ws[c.wo.w + e]; }, [&](int e, float v) { wrl[e] = v; }),
-      rc_seg<1>(tgt ? B : 0, [&](int b) { return X[((c.row0 + b) * d.T + c.Lmax) * p + j]; },
+      rc_seg<1>(tgt ? B : 0, [&](int b) { return xtg[(unsigned)(b * Tp)]; },
                 [&](int b, float v) { xt[b] = v; }),
       rc_seg<1>(p, [&](int cc) { return E[c.eo.A + cc * p + j]; }, [&](int cc, float v) { Acol[cc] = v; }),
       rc_seg<8>(B * K, [&](int e) {  // sum of the nU hidden-chunk partials (fixed order); e = kk * B + b
@@ -232,6 +240,7 @@ __device__ __forceinline__ void fac_bwd_wg(const StepCtx& c, int nUl, int nQ, in
   for (int i = tid; i < Ls; i += RC_BLOCK) lwt[i] = logf((float)(i + 2));
   __syncthreads();
   RC_PHASE(c.ws, c.wo.total, blockIdx.x, 16);
+  RC_PHASE(c.ws, c.wo.total, tbx, 27);
 
   // ---- part 1: mixture x_sim = sum_k w_k y_k, forecast residual, dL/dy and dL/dw (forecast)
   const float gscale = (c.flags & RC_LOSS_FORECAST) ? hy.c_forecast * (2.f / (float)c.Bg) : 0.f;
@@ -397,9 +406,6 @@ __device__ __forceinline__ void fac_bwd_wg(const StepCtx& c, int nUl, int nQ, in
   }
   __syncthreads();
 
-  // trace builds: the update part's phases are recorded by the (network 0, chunk 1) workgroup
-  const int tbx = (kj == 0 && uc == 1 && qc == 0 && role == RC_FB_ALL) ? 0 : 1;
-  (void)tbx;
   RC_PHASE(c.ws, c.wo.total, tbx, 19);
   const RcAdamScalars as = rc_adam_scalars(c, 1, r);
   // ---- part 3: over window tiles of FB_BT (one tile when B <= 128; the first is already staged)
@@ -462,10 +468,7 @@ __device__ __forceinline__ void fac_bwd_wg(const StepCtx& c, int nUl, int nQ, in
             const int bb = e >> 4, u = e & 15;
             return u0 + u < h ? aw[(int64_t)(bt + bb) * h + u0 + u] : 0.f;
           }, [&](int e, float v) { awl[(e >> 4) * (FAC_UC + 1) + (e & 15)] = v; }),
-          rc_seg<32>(nb * FB_QT, [&](int e) {
-            const int bb = e >> 6, qq = e & 63;
-            return q0 + qq < Q ? xwin(c, dL, X, bt + bb, q0 + qq) : 0.f;
-          }, [&](int e, float v) { Xs[(e >> 6) * (FB_QT + 1) + (e & 63)] = v; }));
+          rc_win_seg<32, 6>(rc_win(c, X, bt), slab, nb, q0, Xs, FB_QT + 1, FB_QT));
       __syncthreads();
     }
     if (recompute) {

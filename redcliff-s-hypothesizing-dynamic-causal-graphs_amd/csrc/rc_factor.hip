@@ -67,6 +67,8 @@ int rc_launch_fac_bwd(const StepCtx& c, hipStream_t s, int role, hipEvent_t stop
   const int Q = d.p * d.L;
   const bool upd = (c.flags & RC_STEP_B) && role != RC_FB_RECORDS;
   if (role == RC_FB_UPDATE && !(c.flags & RC_STEP_B)) { rc_set_error("factor update launch without a factor step"); return REDCLIFF_EINVAL; }
+  // (the window tiles and targets are staged with 32-bit offsets from one pointer per workgroup, rc_win)
+  if ((int64_t)d.Bmax * d.T * d.p >= (1ll << 30)) { rc_set_error("factor backward: Bmax*T*p < 2^30 required"); return REDCLIFF_ELIMIT; }
   const int nQ = upd ? (Q + FB_QT - 1) / FB_QT : 1;
   const size_t lds = sizeof(float) * (size_t)fac_bwd_lds_floats(d);
   if (lds > RC_LDS_LIMIT_FLOATS * sizeof(float)) {

@@ -325,21 +325,16 @@ size_t emb_fwd_floats(const RedcliffDims& d, int SB, int w_lds) {
 // a[kj][b][u], partial outputs y[uc][kj][b] = sum_{u in chunk} W1[u] a[b][u] (+ b1 in chunk
 // 0), the chunk's squared layer-0 group norms gq[uc][kj][q] and a snapshot of W1.
 // The whole window block and weight chunk are staged in one pass when p*L <= FQ_MAX.
-template <class Div>
-__device__ inline float xwin(const StepCtx& c, const Div& dL, const float* X, int b, int q) {
-  const int L = c.d.L;
-  const int ch = dL.div(q), t = q - ch * L;
-  return X[((c.row0 + b) * c.d.T + (c.Lmax - L + t)) * c.d.p + ch];
-}
-
+// (trace builds: phase marks 64-67 of factor workgroup 0 -- staged, group norms stored, products
+// done, outputs stored)
 __device__ __attribute__((always_inline)) void fac_fwd_body(const StepCtx& c, int bx, float* sm) {
   const RedcliffDims& d = c.d;
   RC_WG_MARK(c.ws, c.wo.total, RC_KID_FAC_FWD, 0);
   const int nU = rc_nuchunk(d);
-  const int r = rc_rep(c, blockIdx.y), kj = bx / nU, uc = bx - kj * nU;
+  const int r = rc_rep(c, blockIdx.y), kj = RcDiv32(nU, c.mg[RC_MG_NU]).div(bx), uc = bx - kj * nU;
   const int p = d.p, h = d.h, K = d.K;
-  const int k = kj / p, j = kj - k * p;
   const int Q = p * d.L, QT = fq_tile(d), QP = QT + 1;
+  const bool slab = Q <= FQ_MAX;  // QT == Q: a tile row is the window's whole slab, the W0 chunk one range
   const int u0 = uc * FAC_UC;
   const float* P = c.fac + r * c.fs;
   const float* W0 = P + c.fo.W0 + (int64_t)kj * h * Q;
@@ -350,9 +345,11 @@ __device__ __attribute__((always_inline)) void fac_fwd_body(const StepCtx& c, in
   const float* X = c.X + r * c.xr;
   const int tid = threadIdx.x, tb = tid >> 4, tu = tid & 15;
   const int u = u0 + tu;
-  const RcDiv dL(d.L), dQT(QT);
+  const RcDiv32 dQ(Q, c.mg[RC_MG_Q]);
   float* Xs = sm;                // [FK_BT][QT+1]
   float* Ws = Xs + FK_BT * QP;   // [FAC_UC][QT+1]
+  const int nrow = min(FAC_UC, h - u0);  // the chunk's rows below h: nrow * Q contiguous floats of W0
+  const float* W0c = W0 + u0 * Q;        // (32-bit offsets inside the factor slice, as in rc_fac_bwd.h)
   const float bu = u < h ? b0[u] : 0.f, w1 = u < h ? W1[u] : 0.f;
 
   for (int bc = 0; bc < c.B; bc += FK_BT) {
@@ -361,18 +358,23 @@ __device__ __attribute__((always_inline)) void fac_fwd_body(const StepCtx& c, in
     for (int i = 0; i < 8; ++i) acc[i] = 0.f;
     for (int q0 = 0; q0 < Q; q0 += QT) {
       if (q0 > 0 || bc > 0) __syncthreads();
+      // (rows past B of the window tile are not staged: their sums are never stored)
       rc_stage_all(
-          rc_seg<24>(FK_BT * QT, [&](int e) {
-            const int bb = dQT.div(e), qq = e - bb * QT;
-            const int b = bc + bb, q = q0 + qq;
-            return (b < c.B && q < Q) ? xwin(c, dL, X, b, q) : 0.f;
-          }, [&](int e, float v) { Xs[dQT.div(e) * QP + dQT.mod(e)] = v; }),
-          rc_seg<4>(FAC_UC * QT, [&](int e) {
-            const int uu = dQT.div(e), qq = e - uu * QT;
-            const int q = q0 + qq;
-            return (u0 + uu < h && q < Q) ? W0[(int64_t)(u0 + uu) * Q + q] : 0.f;
-          }, [&](int e, float v) { Ws[dQT.div(e) * QP + dQT.mod(e)] = v; }));
+          rc_win_seg<24, 5>(rc_win(c, X, bc), slab, min(FK_BT, c.B - bc), q0, Xs, QP, Q),
+          rc_segc<4>(slab ? nrow * Q : 0, [&](int e) { return W0c[(unsigned)e]; }, [&](int e, float v) {
+            const int uu = dQ.div(e);
+            Ws[uu * QP + e - uu * Q] = v;
+          }),
+          rc_segc<2>(slab ? 0 : FAC_UC * 32, [&](int e) {  // 32-column tiles (QT == 32)
+            const int uu = e >> 5, q = q0 + (e & 31);
+            const bool in = uu < nrow && q < Q;
+            const float w = W0c[(unsigned)(in ? uu * Q + q : 0)];
+            return in ? w : 0.f;
+          }, [&](int e, float v) { Ws[(e >> 5) * QP + (e & 31)] = v; }));
+      if (slab)  // a partial chunk: the rows past h are zero
+        for (int e = nrow * QP + tid; e < FAC_UC * QP; e += RC_BLOCK) Ws[e] = 0.f;
       __syncthreads();
+      if (bc == 0 && q0 == 0) RC_PHASE(c.ws, c.wo.total, bx, 64);
       if (bc == 0)
         for (int qq = tid; qq < QT && q0 + qq < Q; qq += RC_BLOCK) {
           // squared group norms of the chunk's 16 units (GC, models/cmlp.py:162-166), pre-update
@@ -383,6 +385,7 @@ __device__ __attribute__((always_inline)) void fac_fwd_body(const StepCtx& c, in
           }
           ws[c.wo.gq + ((int64_t)uc * K * p + kj) * Q + q0 + qq] = sq;
         }
+      if (bc == 0 && q0 == 0) RC_PHASE(c.ws, c.wo.total, bx, 65);
       const int qn = min(QT, Q - q0);
 #pragma unroll 8
       for (int qq = 0; qq < qn; ++qq) {
@@ -391,6 +394,7 @@ __device__ __attribute__((always_inline)) void fac_fwd_body(const StepCtx& c, in
         for (int i = 0; i < 8; ++i) acc[i] = fmaf(Xs[(tb + 16 * i) * QP + qq], wv, acc[i]);  // rc_fac_bwd.h recomputes this chain
       }
     }
+    if (bc == 0) RC_PHASE(c.ws, c.wo.total, bx, 66);
     if (bc == 0 && tb == 0 && u < h) ws[c.wo.w1 + (int64_t)kj * h + u] = w1;
 #pragma unroll
     for (int i = 0; i < 8; ++i) {
@@ -406,6 +410,7 @@ __device__ __attribute__((always_inline)) void fac_fwd_body(const StepCtx& c, in
       if (tu == 0 && b < c.B) ws[c.wo.y + rc_y_idx(d, uc, kj, b)] = ys + b1;
     }
   }
+  RC_PHASE(c.ws, c.wo.total, bx, 67);
   RC_WG_MARK(c.ws, c.wo.total, RC_KID_FAC_FWD, 1);
 }
 
@@ -481,6 +486,8 @@ void rc_ctx_magics(StepCtx& c) {
   c.mg[RC_MG_ENBW] = rc_magic32(c.enbw);
   c.fzs = Zs;
   c.mg[RC_MG_ZS] = rc_magic32(Zs);
+  c.mg[RC_MG_Q] = rc_magic32((long long)d.p * d.L);
+  c.mg[RC_MG_NU] = rc_magic32(rc_nuchunk(d));
   c.mg[RC_MG_CS] = (unsigned)cs;  // the widths themselves (the slice's width picks its slots)
   c.mg[RC_MG_LS] = (unsigned)ls;
 }
@@ -517,6 +524,8 @@ int rc_launch_forward(const StepCtx& c, hipStream_t s, bool with_emb, bool with_
   int nfac = 0;
   if (with_fac) {
     if (d.h > 128 || d.p * d.L > 4096) { rc_set_error("factor forward: h <= 128 and p*L <= 4096 required"); return REDCLIFF_ELIMIT; }
+    // (the window tiles are staged with 32-bit offsets from one pointer per workgroup, rc_win)
+    if ((int64_t)d.Bmax * d.T * d.p >= (1ll << 30)) { rc_set_error("factor forward: Bmax*T*p < 2^30 required"); return REDCLIFF_ELIMIT; }
     nfac = d.K * d.p * rc_nuchunk(d);
     const size_t f = fac_fwd_floats(d);
     lds = f > lds ? f : lds;

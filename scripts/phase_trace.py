@@ -74,6 +74,17 @@ def main():
     upd = [(i, (ph[i] - t_first) / 100.0) for i in range(19, 24) if ph[i] > 0]
     if upd:  # the (network 0, chunk 1) factor workgroup's update part (rc_fac_bwd.h, trace builds)
         print("factor update WG (network 0, chunk 1) phases at: " + "  ".join("%d %.2f us" % x for x in upd))
+    if ph[16] > 0 and tr[2][0] > 0:  # lead 0's staging pass: its start to mark 16
+        print("fac_bwd lead 0 start->staged (16): %.2f us" % ((ph[16] - tr[2][0]) / 100.0))
+    if ph[26] > 0 and ph[27] > 0:  # the same workgroup's one staging pass: its start (26) to staged (27)
+        print("factor update WG (network 0, chunk 1) start->staged: %.2f us (start at %.2f us)"
+              % ((ph[27] - ph[26]) / 100.0, (ph[26] - t_first) / 100.0))
+    ff = [i for i in range(64, 68) if ph[i] > 0]
+    if ff:  # factor forward workgroup 0 (rc_forward.hip): staged, group norms stored, products done, outputs stored
+        st1 = tr[1][0::2]
+        st0 = int(st1[st1 > 0][0])  # (its slot is its blockIdx.x: the embedder workgroups come first)
+        print("fac_fwd WG0 marks (us after its start; 64 staged, 65 norms, 66 products, 67 stores): " +
+              "  ".join("%d %.2f" % (i, (ph[i] - st0) / 100.0) for i in ff))
     for k, name in enumerate(names):
         st, en = tr[k][0::2], tr[k][1::2]
         ok = (st > 0) & (en > 0)
