@@ -851,6 +851,55 @@ int redcliff_dirspec_nfreq(int32_t nperseg, double fs, double min_freq, double m
 size_t redcliff_dirspec_ws_bytes(int32_t N, int32_t T, int32_t p, int32_t nperseg, int32_t noverlap);
 int redcliff_dirspec_run(const RedcliffDirspecArgs* a, void* stream);
 
+/* ---- SLARAC and QRBS comparison baselines (tidybench/slarac.py, tidybench/qrbs.py) ----
+ * Purely additive entries: REDCLIFF_ABI_VERSION stays 10, no kernel id, no existing entry or layout changes.
+ *
+ * One call solves P x S independent regressions: problem (b, s) is fit s of data set b.
+ * data: [P][T][N] doubles.  With n = T - lags usable rows, sampled row i in [0, n) has the target time t = i + lags,
+ *   the regressors z = [1, x_{t-1}, ..., x_{t-lags}] (D = lags N + 1) and the target
+ *   REDCLIFF_TIDYBENCH_SLARAC: y = x_t;       REDCLIFF_TIDYBENCH_QRBS: y = x_t - x_{t-1}.
+ * idx: the int32 row indices of fit (b, s) start at idx + b idx_pstride + s idx_fstride; count[b][s] of them are
+ *   read.  count -1 = every row 0 .. n - 1 in order (SLARAC's fit of the full data).  max_count bounds every count
+ *   (with -1 counted as n); it sizes the grid and the workspace.  An index outside [0, n), a count above max_count
+ *   or below -1, or ncols outside [1, D] reads nothing out of bounds and gives the fit the status NONFINITE.
+ * ncols: [P][S], SLARAC only (may be NULL for QRBS): the fit solves on the first ncols regressors (efflag N + 1).
+ * SLARAC solves (Z_c Z_c^T) B = Z_c Y^T.  QRBS solves sklearn's Ridge(alpha) with an intercept:
+ *   (Xc^T Xc + alpha I) W = Xc^T yc, X the lags N lag columns, both centred by the resample's own means.  The sums
+ *   are accumulated on data shifted by the full series' column means, and the centring is the rank-one correction
+ *   -k (mu - m)(mu - m)^T applied to those sums; sum x x^T - k mu mu^T is never formed on raw data.
+ * coef: [P][S][N][Dout] doubles, Dout = D for SLARAC (intercept first) and lags N for QRBS; columns past ncols are
+ *   zero; all zero unless the status is OK.
+ * status: [P][S] int32.  The solve is a Cholesky factorisation in double that tracks min_j pivot_j / G_jj
+ *   (pivot_ratio [P][S]); a fit with a ratio below 1e-8, a non-positive pivot or diagonal entry, or no rows is
+ *   SINGULAR (the caller recomputes it with a minimum-norm solver); a non-finite sum gives NONFINITE.
+ * ws: redcliff_tidybench_ws_bytes(P, S, N, lags, max_count) bytes, 16-byte aligned: the series means [P][N] and one
+ *   partial of D (D + 1) / 2 + D N doubles per (fit, chunk of 512 sampled rows).
+ * Limits: N <= 32, lags N <= 96, T > lags >= 1, P and S <= 65535; outside them REDCLIFF_ELIMIT / REDCLIFF_EINVAL,
+ * redcliff_tidybench_supported returns 0 and _ws_bytes returns 0.  All checks precede any HIP call.
+ * Stream-ordered, no host synchronisation, no atomics: rows accumulate in index order within a chunk and chunks in
+ * chunk order, so the same arguments give the same bits and a problem's result does not depend on the batch. */
+#define REDCLIFF_TIDYBENCH_SLARAC 0
+#define REDCLIFF_TIDYBENCH_QRBS 1
+#define REDCLIFF_TIDYBENCH_OK 0
+#define REDCLIFF_TIDYBENCH_SINGULAR 1
+#define REDCLIFF_TIDYBENCH_NONFINITE 2
+typedef struct RedcliffTidybenchArgs {
+  int32_t mode, P, S, T, N, lags;
+  int32_t max_count, pad_;
+  double alpha;                  /* QRBS only (> 0)                                                        */
+  const double* data;
+  const int32_t* idx; int64_t idx_pstride, idx_fstride;
+  const int32_t* count;
+  const int32_t* ncols;
+  double* coef;
+  int32_t* status;
+  double* pivot_ratio;
+  void* ws; size_t ws_bytes;
+} RedcliffTidybenchArgs;
+int redcliff_tidybench_supported(int32_t T, int32_t N, int32_t lags);
+size_t redcliff_tidybench_ws_bytes(int32_t P, int32_t S, int32_t N, int32_t lags, int32_t max_count);
+int redcliff_tidybench_run(const RedcliffTidybenchArgs* a, void* stream);
+
 /* Per-kernel HIP-event timing for benchmarking: redcliff_kernel_timing(1) brackets every
  * kernel launched by redcliff_train_step with events on its stream; redcliff_kernel_times()
  * synchronises them and returns per-kernel totals (ids 0..11: supports, emb_fwd, fac_fwd,

@@ -19,6 +19,8 @@ from .navar_lstm import NAVARLSTM, fit_navar_lstm_baselines
 from .dcsfa_nmf import DcsfaFitPack, DcsfaNmf, FullDCSFAModel, FullDCSFAModel_GCv2, NmfBase, fit_dcsfa_baselines
 from .directed_spectrum import (DEFAULT_CSD_PARAMS, directed_spectrum_features, flatten_directed_spectrum_features,
                                 get_directed_spectrum, make_high_level_signal_features)
+from .tidybench import (get_standardized_off_diagonal_relation_predictions, prepare_data_for_modeling, qrbs, qrbs_many,
+                        run_tidybench_experiment, slarac, slarac_many)
 from .data import (load_normalized_DREAM4_data_train_test_split_as_matrices,
                    load_normalized_lfp_data_train_test_split_as_matrices)
 
@@ -30,5 +32,7 @@ __all__ = ["MLP", "cMLP", "DGCNN", "DGCNN_Model", "DGCNN_Embedder", "cEmbedder",
            "NmfBase", "DcsfaNmf", "FullDCSFAModel", "FullDCSFAModel_GCv2", "DcsfaFitPack", "fit_dcsfa_baselines",
            "DEFAULT_CSD_PARAMS", "get_directed_spectrum", "make_high_level_signal_features",
            "flatten_directed_spectrum_features", "directed_spectrum_features",
+           "slarac", "qrbs", "slarac_many", "qrbs_many", "run_tidybench_experiment", "prepare_data_for_modeling",
+           "get_standardized_off_diagonal_relation_predictions",
            "load_normalized_DREAM4_data_train_test_split_as_matrices",
            "load_normalized_lfp_data_train_test_split_as_matrices"]

@@ -49,7 +49,8 @@ EXPORTED = ("redcliff_abi_version", "redcliff_last_error", "redcliff_workspace_b
             "redcliff_navar_lstm_supported", "redcliff_navar_lstm_ws_floats", "redcliff_navar_lstm_run",
             "redcliff_dgcnn_fit_supported", "redcliff_dgcnn_fit_ws_floats", "redcliff_dgcnn_fit_run",
             "redcliff_dcsfa_supported", "redcliff_dcsfa_ws_floats", "redcliff_dcsfa_run",
-            "redcliff_dirspec_supported", "redcliff_dirspec_nfreq", "redcliff_dirspec_ws_bytes", "redcliff_dirspec_run")
+            "redcliff_dirspec_supported", "redcliff_dirspec_nfreq", "redcliff_dirspec_ws_bytes", "redcliff_dirspec_run",
+            "redcliff_tidybench_supported", "redcliff_tidybench_ws_bytes", "redcliff_tidybench_run")
 CEMB_WS_REGIONS = ("ha", "w1", "g", "g0", "E", "E0", "dE", "draw")
 KERNEL_IDS = ("supports", "emb_fwd", "fac_fwd", "fac_bwd", "emb_bwd", "emb_final", "fac_mix", "emb_combine", "fac_lead",
               "score", "score_graphs", "score_cemb")
@@ -182,6 +183,14 @@ class DirspecArgs(ctypes.Structure):
         ("ws", _vp), ("ws_bytes", ctypes.c_size_t), ("status", _vp), ("iters", _vp)]
 
 
+class TidybenchArgs(ctypes.Structure):
+    """RedcliffTidybenchArgs (redcliff_tidybench_run)."""
+    _fields_ = [(n, ctypes.c_int32) for n in ("mode", "P", "S", "T", "N", "lags", "max_count", "pad_")] + [
+        ("alpha", ctypes.c_double), ("data", _vp), ("idx", _vp), ("idx_pstride", _i64), ("idx_fstride", _i64),
+        ("count", _vp), ("ncols", _vp), ("coef", _vp), ("status", _vp), ("pivot_ratio", _vp),
+        ("ws", _vp), ("ws_bytes", ctypes.c_size_t)]
+
+
 def adam_hyper(lr, betas, eps, weight_decay):
     b1, b2 = float(betas[0]), float(betas[1])
     return AdamHyper(float(lr), b1, b2, float(eps), float(weight_decay), b2, 1.0 - b1, 1.0 - b2, 0)
@@ -270,12 +279,16 @@ def lib():
     L.redcliff_dirspec_nfreq.argtypes = [ctypes.c_int32, ctypes.c_double, ctypes.c_double, ctypes.c_double]
     L.redcliff_dirspec_ws_bytes.argtypes = [ctypes.c_int32] * 5
     L.redcliff_dirspec_run.argtypes = [ctypes.POINTER(DirspecArgs), _vp]
+    L.redcliff_tidybench_supported.argtypes = [ctypes.c_int32] * 3
+    L.redcliff_tidybench_ws_bytes.argtypes = [ctypes.c_int32] * 5
+    L.redcliff_tidybench_run.argtypes = [ctypes.POINTER(TidybenchArgs), _vp]
     for name in EXPORTED[2:]:
         if name not in ("redcliff_workspace_bytes", "redcliff_emb_param_count", "redcliff_fac_param_count",
                         "redcliff_build_id", "redcliff_cemb_param_count", "redcliff_cemb_workspace_bytes",
                         "redcliff_score_recording_workspace_bytes",
                         "redcliff_score_recording_pack_workspace_bytes", "redcliff_navar_lstm_ws_floats",
-                        "redcliff_dgcnn_fit_ws_floats", "redcliff_dcsfa_ws_floats", "redcliff_dirspec_ws_bytes"):
+                        "redcliff_dgcnn_fit_ws_floats", "redcliff_dcsfa_ws_floats", "redcliff_dirspec_ws_bytes",
+                        "redcliff_tidybench_ws_bytes"):
             getattr(L, name).restype = ctypes.c_int
     L.redcliff_cemb_param_count.restype = ctypes.c_size_t
     L.redcliff_cemb_workspace_bytes.restype = ctypes.c_size_t
@@ -285,6 +298,7 @@ def lib():
     L.redcliff_dgcnn_fit_ws_floats.restype = ctypes.c_int64
     L.redcliff_dcsfa_ws_floats.restype = ctypes.c_int64
     L.redcliff_dirspec_ws_bytes.restype = ctypes.c_size_t
+    L.redcliff_tidybench_ws_bytes.restype = ctypes.c_size_t
     L.redcliff_build_id.restype = ctypes.c_char_p
     if L.redcliff_abi_version() != ABI_VERSION:
         raise ImportError("libredcliff_hip.so ABI %d != %d" % (L.redcliff_abi_version(), ABI_VERSION))
