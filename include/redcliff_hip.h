@@ -900,6 +900,59 @@ int redcliff_tidybench_supported(int32_t T, int32_t N, int32_t lags);
 size_t redcliff_tidybench_ws_bytes(int32_t P, int32_t S, int32_t N, int32_t lags, int32_t max_count);
 int redcliff_tidybench_run(const RedcliffTidybenchArgs* a, void* stream);
 
+/* ---- DYNOTEARS comparison baseline (models/causalnex_dynotears_vanilla.py, models/dynotears_vanilla.py) ----
+ * Purely additive entries: REDCLIFF_ABI_VERSION stays 10, no kernel id, no existing entry or layout changes.
+ *
+ * One call advances P independent problems (one per recording and lambda).  Problem b has n_rows[b] rows
+ *   X row r:     X     + b x_pstride  + r x_rstride,  d contiguous values;
+ *   Xlags row r: Xlags + b xl_pstride + r xl_rstride, p d contiguous values (lag 1 first),
+ * float32 or float64 (dtype; strides in elements), so two views of one [P][T][d] buffer serve as X and Xlags.
+ * Variables: wa[2 (p + 1) d^2] >= 0, viewed as (2 (p + 1) d) x d: rows [0, d) are W+, rows [d, 2d) W-, then per lag
+ * the d x d block A+ followed by A-; W = W+ - W-, A = A+ - A-.  fixed[nv] (shared by the batch) marks the entries whose
+ * bounds are (0, 0): both copies of W's diagonal and the tabu entries.  The problem minimises
+ *   0.5/n ||X (I - W) - Xlags A||_F^2 + lambda_w[b] sum wa[:2 d^2] + lambda_a[b] sum wa[2 d^2:]   s.t. tr expm(W o W) = d
+ * by the reference's augmented-Lagrangian loop (max_iter, h_tol, rho0 = 1, alpha0 = 0, rho_max = 1e20) around a
+ * limited-memory projected quasi-Newton solver that stops by L-BFGS-B's rules (m pairs, factr, pgtol, maxiter,
+ * maxfun, maxls; scipy's defaults are 10, 1e7, 1e-5, 15000, 15000, 20).  rho0 = 0 is accepted with max_iter = 1 only.
+ * start != 0 forms the Gram matrices and resets every problem; every call then advances each unfinished problem by at
+ * most evals_per_launch evaluations and stores in *remaining (device memory) how many are still unfinished: call again
+ * with start = 0 and the same buffers until it reads 0.  The state between calls is in ws.
+ * Outputs of a finished problem: W [P][d][d], A [P][p d][d], wa [P][nv] (may be NULL), status [P],
+ *   stats [P][6]: h, rho, alpha, f and projected-gradient norm at the end of the last inner solve, failed line searches;
+ *   counts [P][6]: outer iterations, inner solves, quasi-Newton iterations, evaluations, non-finite trial values, launches.
+ * A non-finite Gram entry or a recording without rows gives NONFINITE and NaN outputs.  A non-finite trial value counts
+ * as larger than any finite one (the step shrinks); it is counted, and x never becomes non-finite.
+ * Limits: d <= 12, (p + 1) d <= 24, m <= 16; outside them REDCLIFF_ELIMIT, redcliff_dynotears_supported returns 0
+ * and _ws_bytes returns 0.  All checks precede any HIP call.  Stream-ordered, no host synchronisation; every sum runs
+ * in a fixed order, so the same arguments give the same bits whatever the batch and whatever evals_per_launch. */
+#define REDCLIFF_DYNOTEARS_F32 0
+#define REDCLIFF_DYNOTEARS_F64 1
+#define REDCLIFF_DYNOTEARS_CONVERGED 0
+#define REDCLIFF_DYNOTEARS_MAXITER 1
+#define REDCLIFF_DYNOTEARS_RHO_CAP 2
+#define REDCLIFF_DYNOTEARS_NONFINITE 3
+typedef struct RedcliffDynotearsArgs {
+  int32_t P, d, p, dtype;
+  int32_t start, evals_per_launch;
+  int32_t max_iter, m, maxiter, maxfun, maxls, pad_;
+  double h_tol, rho0, alpha0, rho_max, factr, pgtol;
+  const void* X; int64_t x_pstride, x_rstride;
+  const void* Xlags; int64_t xl_pstride, xl_rstride;
+  const int32_t* n_rows;
+  const double* lambda_w;
+  const double* lambda_a;
+  const uint8_t* fixed;
+  double* W; double* A; double* wa;
+  int32_t* status;
+  double* stats;
+  int32_t* counts;
+  int32_t* remaining;
+  void* ws; size_t ws_bytes;
+} RedcliffDynotearsArgs;
+int redcliff_dynotears_supported(int32_t d, int32_t p);
+size_t redcliff_dynotears_ws_bytes(int32_t P, int32_t d, int32_t p, int32_t m);
+int redcliff_dynotears_run(const RedcliffDynotearsArgs* a, void* stream);
+
 /* Per-kernel HIP-event timing for benchmarking: redcliff_kernel_timing(1) brackets every
  * kernel launched by redcliff_train_step with events on its stream; redcliff_kernel_times()
  * synchronises them and returns per-kernel totals (ids 0..11: supports, emb_fwd, fac_fwd,

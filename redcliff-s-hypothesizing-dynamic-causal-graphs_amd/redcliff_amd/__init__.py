@@ -21,7 +21,9 @@ from .directed_spectrum import (DEFAULT_CSD_PARAMS, directed_spectrum_features, 
                                 get_directed_spectrum, make_high_level_signal_features)
 from .tidybench import (get_standardized_off_diagonal_relation_predictions, prepare_data_for_modeling, qrbs, qrbs_many,
                         run_tidybench_experiment, slarac, slarac_many)
+from .dynotears_vanilla import DYNOTEARS_Model, fit_dynotears_baselines, from_numpy_dynamic, from_numpy_dynamic_many
 from .data import (load_normalized_DREAM4_data_train_test_split_as_matrices,
+                   load_normalized_DREAM4_data_train_test_split_as_tensors,
                    load_normalized_lfp_data_train_test_split_as_matrices)
 
 __all__ = ["MLP", "cMLP", "DGCNN", "DGCNN_Model", "DGCNN_Embedder", "cEmbedder", "MLPClassifierForSingleObjective",
@@ -34,5 +36,7 @@ __all__ = ["MLP", "cMLP", "DGCNN", "DGCNN_Model", "DGCNN_Embedder", "cEmbedder",
            "flatten_directed_spectrum_features", "directed_spectrum_features",
            "slarac", "qrbs", "slarac_many", "qrbs_many", "run_tidybench_experiment", "prepare_data_for_modeling",
            "get_standardized_off_diagonal_relation_predictions",
+           "DYNOTEARS_Model", "fit_dynotears_baselines", "from_numpy_dynamic", "from_numpy_dynamic_many",
            "load_normalized_DREAM4_data_train_test_split_as_matrices",
+           "load_normalized_DREAM4_data_train_test_split_as_tensors",
            "load_normalized_lfp_data_train_test_split_as_matrices"]

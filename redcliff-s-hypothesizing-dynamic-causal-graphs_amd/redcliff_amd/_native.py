@@ -50,7 +50,8 @@ EXPORTED = ("redcliff_abi_version", "redcliff_last_error", "redcliff_workspace_b
             "redcliff_dgcnn_fit_supported", "redcliff_dgcnn_fit_ws_floats", "redcliff_dgcnn_fit_run",
             "redcliff_dcsfa_supported", "redcliff_dcsfa_ws_floats", "redcliff_dcsfa_run",
             "redcliff_dirspec_supported", "redcliff_dirspec_nfreq", "redcliff_dirspec_ws_bytes", "redcliff_dirspec_run",
-            "redcliff_tidybench_supported", "redcliff_tidybench_ws_bytes", "redcliff_tidybench_run")
+            "redcliff_tidybench_supported", "redcliff_tidybench_ws_bytes", "redcliff_tidybench_run",
+            "redcliff_dynotears_supported", "redcliff_dynotears_ws_bytes", "redcliff_dynotears_run")
 CEMB_WS_REGIONS = ("ha", "w1", "g", "g0", "E", "E0", "dE", "draw")
 KERNEL_IDS = ("supports", "emb_fwd", "fac_fwd", "fac_bwd", "emb_bwd", "emb_final", "fac_mix", "emb_combine", "fac_lead",
               "score", "score_graphs", "score_cemb")
@@ -191,6 +192,16 @@ class TidybenchArgs(ctypes.Structure):
         ("ws", _vp), ("ws_bytes", ctypes.c_size_t)]
 
 
+class DynotearsArgs(ctypes.Structure):
+    """RedcliffDynotearsArgs (redcliff_dynotears_run)."""
+    _fields_ = [(n, ctypes.c_int32) for n in ("P", "d", "p", "dtype", "start", "evals_per_launch", "max_iter", "m", "maxiter",
+                                               "maxfun", "maxls", "pad_")] + [
+        (n, ctypes.c_double) for n in ("h_tol", "rho0", "alpha0", "rho_max", "factr", "pgtol")] + [
+        ("X", _vp), ("x_pstride", _i64), ("x_rstride", _i64), ("Xlags", _vp), ("xl_pstride", _i64), ("xl_rstride", _i64),
+        ("n_rows", _vp), ("lambda_w", _vp), ("lambda_a", _vp), ("fixed", _vp), ("W", _vp), ("A", _vp), ("wa", _vp),
+        ("status", _vp), ("stats", _vp), ("counts", _vp), ("remaining", _vp), ("ws", _vp), ("ws_bytes", ctypes.c_size_t)]
+
+
 def adam_hyper(lr, betas, eps, weight_decay):
     b1, b2 = float(betas[0]), float(betas[1])
     return AdamHyper(float(lr), b1, b2, float(eps), float(weight_decay), b2, 1.0 - b1, 1.0 - b2, 0)
@@ -282,13 +293,16 @@ def lib():
     L.redcliff_tidybench_supported.argtypes = [ctypes.c_int32] * 3
     L.redcliff_tidybench_ws_bytes.argtypes = [ctypes.c_int32] * 5
     L.redcliff_tidybench_run.argtypes = [ctypes.POINTER(TidybenchArgs), _vp]
+    L.redcliff_dynotears_supported.argtypes = [ctypes.c_int32] * 2
+    L.redcliff_dynotears_ws_bytes.argtypes = [ctypes.c_int32] * 4
+    L.redcliff_dynotears_run.argtypes = [ctypes.POINTER(DynotearsArgs), _vp]
     for name in EXPORTED[2:]:
         if name not in ("redcliff_workspace_bytes", "redcliff_emb_param_count", "redcliff_fac_param_count",
                         "redcliff_build_id", "redcliff_cemb_param_count", "redcliff_cemb_workspace_bytes",
                         "redcliff_score_recording_workspace_bytes",
                         "redcliff_score_recording_pack_workspace_bytes", "redcliff_navar_lstm_ws_floats",
                         "redcliff_dgcnn_fit_ws_floats", "redcliff_dcsfa_ws_floats", "redcliff_dirspec_ws_bytes",
-                        "redcliff_tidybench_ws_bytes"):
+                        "redcliff_tidybench_ws_bytes", "redcliff_dynotears_ws_bytes"):
             getattr(L, name).restype = ctypes.c_int
     L.redcliff_cemb_param_count.restype = ctypes.c_size_t
     L.redcliff_cemb_workspace_bytes.restype = ctypes.c_size_t
@@ -299,6 +313,7 @@ def lib():
     L.redcliff_dcsfa_ws_floats.restype = ctypes.c_int64
     L.redcliff_dirspec_ws_bytes.restype = ctypes.c_size_t
     L.redcliff_tidybench_ws_bytes.restype = ctypes.c_size_t
+    L.redcliff_dynotears_ws_bytes.restype = ctypes.c_size_t
     L.redcliff_build_id.restype = ctypes.c_char_p
     if L.redcliff_abi_version() != ABI_VERSION:
         raise ImportError("libredcliff_hip.so ABI %d != %d" % (L.redcliff_abi_version(), ABI_VERSION))

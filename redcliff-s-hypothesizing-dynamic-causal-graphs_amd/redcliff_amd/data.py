@@ -387,6 +387,23 @@ def load_normalized_DREAM4_data_train_test_split_as_matrices(data_root_path, sig
     return tuple(out)
 
 
+def load_normalized_DREAM4_data_train_test_split_as_tensors(data_root_path, signal_format="original", shuffle=True, shuffle_seed=0,
+                                                            max_num_features_per_series=None, train_portion=0.8, dirspec_params=None,
+                                                            grid_search=True):
+    """dream4_datasets.py:273-351 -> X_train [N, T, p], y_train, X_val, y_val (numpy float32): whole normalised
+    recordings, the input of the DYNOTEARS (Vanilla) and NAVAR drivers.  The reference asserts two-dimensional items,
+    so the flattened and feature formats are refused here."""
+    if any(k in signal_format for k in ("flattened", "directed_spectrum", "power_features")):
+        raise ValueError("the *_as_tensors loader returns whole recordings: signal_format %r" % signal_format)
+    tp, vp = _split_dirs(data_root_path, train_portion, lambda x: "subset_" in x)
+    out = []
+    for path in (tp, vp):
+        ds = NormalizedRecordingDirectory(path, "dream4", shuffle, shuffle_seed, grid_search)
+        Xn, _ = ds.materialize()
+        out.extend((Xn.numpy(), _label_matrix([ds.labels[i] for i in ds.data])))
+    return tuple(out)
+
+
 def load_normalized_lfp_data_train_test_split_as_matrices(data_root_path, signal_format="original flattened", shuffle=True,
                                                           shuffle_seed=0, max_num_features_per_series=25, train_portion=0.8,
                                                           dirspec_params=None, grid_search=True, average_region_map=None,

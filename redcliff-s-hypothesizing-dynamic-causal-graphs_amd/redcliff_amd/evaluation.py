@@ -259,8 +259,12 @@ def get_model_gc_estimates(model, model_type, num_ests_required, X=None):
     mode yields one graph."""
     if "DCSFA" in model_type:  # eval_utils.py:936-937: one (nodes, nodes) array per factor
         return model.GC(threshold=False, ignore_features=True)
+    if "DYNOTEARS" in model_type:  # eval_utils.py:928-934: the one (nodes, nodes) estimate, replicated
+        import copy
+        est = model.GC()
+        return [copy.deepcopy(est) for _ in range(num_ests_required)]
     if "REDCLIFF" not in model_type:
-        raise NotImplementedError("only REDCLIFF and DCSFA models are part of this build (model_type=%r)" % model_type)
+        raise NotImplementedError("only REDCLIFF, DCSFA and DYNOTEARS models are part of this build (model_type=%r)" % model_type)
     by_sample = model.GC(model.primary_gc_est_mode, X=X, threshold=False, ignore_lag=False,
                          combine_wavelet_representations=True, rank_wavelets=False)
     assert len(by_sample) == 1
