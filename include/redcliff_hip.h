@@ -900,6 +900,48 @@ int redcliff_tidybench_supported(int32_t T, int32_t N, int32_t lags);
 size_t redcliff_tidybench_ws_bytes(int32_t P, int32_t S, int32_t N, int32_t lags, int32_t max_count);
 int redcliff_tidybench_run(const RedcliffTidybenchArgs* a, void* stream);
 
+/* ---- LASAR comparison baseline (tidybench/lasar.py; sklearn's LassoLarsCV underneath) ----
+ * Purely additive entries: REDCLIFF_ABI_VERSION stays 10, no kernel id, no existing entry or layout changes.
+ *
+ * One call runs P x S x N cross-validated lasso selections and refits (lags = 1): fit (b, s) is count[b][s] sampled
+ * rows of data[b] ([P][T][N] doubles; idx, count, max_count and the strides as for redcliff_tidybench_run, count -1 =
+ * every row in order), target j is channel j at time t regressed on all channels at t - 1.  KFold(cv) without
+ * shuffling cuts the gathered rows into cv contiguous folds, the first count % cv one row longer.  Per target: the cv
+ * fold paths of sklearn's lasso-LARS solver on the training rows' centred Gram matrix, the folds' alphas merged, the
+ * mean squared held-out residual at each (the quadratic form of the linearly interpolated coefficients in the held-out
+ * rows' sums), the argmin, the final path on all rows down to that alpha, and a Cholesky refit of the parents with a
+ * positive coefficient on the uncentred sums under the pivot rule of redcliff_tidybench_run.
+ * coef: [P][S][N][N] (target, parent), zero off the selection and unless the status is OK.  best_alpha [P][S][N];
+ * best_index [P][S][N]: its index among the merged alphas with finite errors; selected [P][S][N]: bit i = parent i.
+ * status [P][S][N]: OK; SINGULAR (the refit refused by the pivot rule, pivot_ratio [P][S][N] below 1e-8);
+ *   DEGENERATE: a path met the solver's drop-for-good, alpha-increasing or non-finite-AA branch, dropped several
+ *   coefficients in one step, stored more than 2 N + 4 knots or ended on a rising alpha, a fold trains on no more than
+ *   N rows, or no alpha has a finite error (the caller recomputes the target on the host); NONFINITE: a non-finite
+ *   sum, an index outside [0, T - 1), a count below cv or above max_count.
+ * ws: redcliff_lasar_ws_bytes(P, S, N, lags, cv, max_count) bytes, 16-byte aligned.
+ * Limits: N <= 16, lags == 1, 2 <= cv <= 8, P and S <= 65535; outside them REDCLIFF_ELIMIT / REDCLIFF_EINVAL,
+ * redcliff_lasar_supported returns 0 and _ws_bytes returns 0.  All checks precede any HIP call.
+ * Stream-ordered, no host synchronisation, no atomics, fixed summation orders that depend on the fit's count and cv
+ * alone: the same arguments give the same bits and a target's result does not depend on the rest of the batch. */
+#define REDCLIFF_LASAR_DEGENERATE 3
+typedef struct RedcliffLasarArgs {
+  int32_t P, S, T, N, lags, cv;
+  int32_t max_count, pad_;
+  const double* data;
+  const int32_t* idx; int64_t idx_pstride, idx_fstride;
+  const int32_t* count;
+  double* coef;
+  double* best_alpha;
+  int32_t* best_index;
+  int32_t* selected;
+  int32_t* status;
+  double* pivot_ratio;
+  void* ws; size_t ws_bytes;
+} RedcliffLasarArgs;
+int redcliff_lasar_supported(int32_t T, int32_t N, int32_t lags);
+size_t redcliff_lasar_ws_bytes(int32_t P, int32_t S, int32_t N, int32_t lags, int32_t cv, int32_t max_count);
+int redcliff_lasar_run(const RedcliffLasarArgs* a, void* stream);
+
 /* ---- DYNOTEARS comparison baseline (models/causalnex_dynotears_vanilla.py, models/dynotears_vanilla.py) ----
  * Purely additive entries: REDCLIFF_ABI_VERSION stays 10, no kernel id, no existing entry or layout changes.
  *

@@ -19,8 +19,8 @@ from .navar_lstm import NAVARLSTM, fit_navar_lstm_baselines
 from .dcsfa_nmf import DcsfaFitPack, DcsfaNmf, FullDCSFAModel, FullDCSFAModel_GCv2, NmfBase, fit_dcsfa_baselines
 from .directed_spectrum import (DEFAULT_CSD_PARAMS, directed_spectrum_features, flatten_directed_spectrum_features,
                                 get_directed_spectrum, make_high_level_signal_features)
-from .tidybench import (get_standardized_off_diagonal_relation_predictions, prepare_data_for_modeling, qrbs, qrbs_many,
-                        run_tidybench_experiment, slarac, slarac_many)
+from .tidybench import (get_standardized_off_diagonal_relation_predictions, lasar, lasar_many, prepare_data_for_modeling, qrbs,
+                        qrbs_many, run_lasar_experiment, run_tidybench_experiment, slarac, slarac_many)
 from .dynotears_vanilla import DYNOTEARS_Model, fit_dynotears_baselines, from_numpy_dynamic, from_numpy_dynamic_many
 from .data import (load_normalized_DREAM4_data_train_test_split_as_matrices,
                    load_normalized_DREAM4_data_train_test_split_as_tensors,
@@ -34,7 +34,7 @@ __all__ = ["MLP", "cMLP", "DGCNN", "DGCNN_Model", "DGCNN_Embedder", "cEmbedder",
            "NmfBase", "DcsfaNmf", "FullDCSFAModel", "FullDCSFAModel_GCv2", "DcsfaFitPack", "fit_dcsfa_baselines",
            "DEFAULT_CSD_PARAMS", "get_directed_spectrum", "make_high_level_signal_features",
            "flatten_directed_spectrum_features", "directed_spectrum_features",
-           "slarac", "qrbs", "slarac_many", "qrbs_many", "run_tidybench_experiment", "prepare_data_for_modeling",
+           "slarac", "qrbs", "slarac_many", "qrbs_many", "lasar", "lasar_many", "run_lasar_experiment", "run_tidybench_experiment", "prepare_data_for_modeling",
            "get_standardized_off_diagonal_relation_predictions",
            "DYNOTEARS_Model", "fit_dynotears_baselines", "from_numpy_dynamic", "from_numpy_dynamic_many",
            "load_normalized_DREAM4_data_train_test_split_as_matrices",

@@ -51,7 +51,8 @@ EXPORTED = ("redcliff_abi_version", "redcliff_last_error", "redcliff_workspace_b
             "redcliff_dcsfa_supported", "redcliff_dcsfa_ws_floats", "redcliff_dcsfa_run",
             "redcliff_dirspec_supported", "redcliff_dirspec_nfreq", "redcliff_dirspec_ws_bytes", "redcliff_dirspec_run",
             "redcliff_tidybench_supported", "redcliff_tidybench_ws_bytes", "redcliff_tidybench_run",
-            "redcliff_dynotears_supported", "redcliff_dynotears_ws_bytes", "redcliff_dynotears_run")
+            "redcliff_dynotears_supported", "redcliff_dynotears_ws_bytes", "redcliff_dynotears_run",
+            "redcliff_lasar_supported", "redcliff_lasar_ws_bytes", "redcliff_lasar_run")
 CEMB_WS_REGIONS = ("ha", "w1", "g", "g0", "E", "E0", "dE", "draw")
 KERNEL_IDS = ("supports", "emb_fwd", "fac_fwd", "fac_bwd", "emb_bwd", "emb_final", "fac_mix", "emb_combine", "fac_lead",
               "score", "score_graphs", "score_cemb")
@@ -192,6 +193,14 @@ class TidybenchArgs(ctypes.Structure):
         ("ws", _vp), ("ws_bytes", ctypes.c_size_t)]
 
 
+class LasarArgs(ctypes.Structure):
+    """RedcliffLasarArgs (redcliff_lasar_run)."""
+    _fields_ = [(n, ctypes.c_int32) for n in ("P", "S", "T", "N", "lags", "cv", "max_count", "pad_")] + [
+        ("data", _vp), ("idx", _vp), ("idx_pstride", _i64), ("idx_fstride", _i64), ("count", _vp), ("coef", _vp),
+        ("best_alpha", _vp), ("best_index", _vp), ("selected", _vp), ("status", _vp), ("pivot_ratio", _vp),
+        ("ws", _vp), ("ws_bytes", ctypes.c_size_t)]
+
+
 class DynotearsArgs(ctypes.Structure):
     """RedcliffDynotearsArgs (redcliff_dynotears_run)."""
     _fields_ = [(n, ctypes.c_int32) for n in ("P", "d", "p", "dtype", "start", "evals_per_launch", "max_iter", "m", "maxiter",
@@ -296,13 +305,16 @@ def lib():
     L.redcliff_dynotears_supported.argtypes = [ctypes.c_int32] * 2
     L.redcliff_dynotears_ws_bytes.argtypes = [ctypes.c_int32] * 4
     L.redcliff_dynotears_run.argtypes = [ctypes.POINTER(DynotearsArgs), _vp]
+    L.redcliff_lasar_supported.argtypes = [ctypes.c_int32] * 3
+    L.redcliff_lasar_ws_bytes.argtypes = [ctypes.c_int32] * 6
+    L.redcliff_lasar_run.argtypes = [ctypes.POINTER(LasarArgs), _vp]
     for name in EXPORTED[2:]:
         if name not in ("redcliff_workspace_bytes", "redcliff_emb_param_count", "redcliff_fac_param_count",
                         "redcliff_build_id", "redcliff_cemb_param_count", "redcliff_cemb_workspace_bytes",
                         "redcliff_score_recording_workspace_bytes",
                         "redcliff_score_recording_pack_workspace_bytes", "redcliff_navar_lstm_ws_floats",
                         "redcliff_dgcnn_fit_ws_floats", "redcliff_dcsfa_ws_floats", "redcliff_dirspec_ws_bytes",
-                        "redcliff_tidybench_ws_bytes", "redcliff_dynotears_ws_bytes"):
+                        "redcliff_tidybench_ws_bytes", "redcliff_dynotears_ws_bytes", "redcliff_lasar_ws_bytes"):
             getattr(L, name).restype = ctypes.c_int
     L.redcliff_cemb_param_count.restype = ctypes.c_size_t
     L.redcliff_cemb_workspace_bytes.restype = ctypes.c_size_t
@@ -314,6 +326,7 @@ def lib():
     L.redcliff_dirspec_ws_bytes.restype = ctypes.c_size_t
     L.redcliff_tidybench_ws_bytes.restype = ctypes.c_size_t
     L.redcliff_dynotears_ws_bytes.restype = ctypes.c_size_t
+    L.redcliff_lasar_ws_bytes.restype = ctypes.c_size_t
     L.redcliff_build_id.restype = ctypes.c_char_p
     if L.redcliff_abi_version() != ABI_VERSION:
         raise ImportError("libredcliff_hip.so ABI %d != %d" % (L.redcliff_abi_version(), ABI_VERSION))

@@ -1,4 +1,4 @@
-"""The regime-aware tidybench comparison baselines: SLARAC and QRBS.
+"""The regime-aware tidybench comparison baselines: SLARAC and QRBS, and (second half of the file) LASAR.
 
 Restated from the reference's ``tidybench/slarac.py``, ``tidybench/qrbs.py``, ``tidybench/utils.py`` and
 ``run_tidybench_experiment`` / ``prepare_data_for_modeling`` of ``evaluate/eval_algs_by_d4icMSNR.py``.
@@ -24,6 +24,13 @@ reference returns.  Regime-masked series make this case common.
 
 REDCLIFF_TIDYBENCH_PATH=fused|host|auto selects the route (auto: the device when a GPU and the library are
 present and the shape is supported).  sklearn and scipy are not imported.
+
+LASAR (``lasar``, ``lasar_many``, ``run_lasar_experiment``) is ``tidybench/lasar.py``: per fit and target sklearn's
+``LassoLarsCV`` selects the parents with a positive coefficient and a least-squares refit on them gives the scores.
+Its draws are SLARAC's without the effective lags.  The device route (``redcliff_lasar_run``, csrc/rc_lasar.hip) runs
+every fold path, alpha choice, final path and refit of a batch from per-fold Gram sums; the host route restates what
+sklearn executes, branch by branch, and also recomputes the (series, fit, target) triples the device flags SINGULAR
+or DEGENERATE.
 """
 import os
 import time
@@ -507,12 +514,537 @@ def run_tidybench_experiment(samples, alg_name):
     masked to that regime's rows, ``post_standardise=True``, |.| with a zero diagonal.  The R masked series go
     through one ``*_many`` call."""
     if alg_name == "lasar":
-        raise NotImplementedError("lasar is not ported: it runs sklearn's cross-validated LARS path (LassoLarsCV), a "
-                                  "sequential active-set algorithm with no batched native form here (DESIGN section 10)")
+        raise NotImplementedError("lasar has its own driver, run_lasar_experiment(samples): the cross-validated LARS "
+                                  "paths (LassoLarsCV) run through lasar_many, not through this function (DESIGN section 24)")
     if alg_name not in ("slarac", "qrbs"):
         raise ValueError("unknown tidybench algorithm %r" % (alg_name,))
     data, _, masks, _, _, _, R = prepare_data_for_modeling(samples)
     series = np.stack([data * masks[r] for r in range(R)])
     fn = slarac_many if alg_name == "slarac" else qrbs_many
     scores = fn(series, post_standardise=True)
+    return [get_standardized_off_diagonal_relation_predictions(scores[r], transpose=False) for r in range(R)]
+
+
+# ========================================================================================
+# LASAR (tidybench/lasar.py): LassoLarsCV variable selection per target, then a least-squares refit
+# ========================================================================================
+DEGENERATE = 3            # LS_DEGENERATE of csrc/rc_lasar.h: the (series, fit, target) is recomputed on the host
+LARS_MAX_ITER = 500       # LassoLarsCV's max_iter
+LARS_MAX_N_ALPHAS = 1000  # LassoLarsCV's max_n_alphas
+_EPS = float(np.finfo(np.float64).eps)
+_TINY32 = float(np.finfo(np.float32).tiny)
+_EQ_TOL = float(np.finfo(np.float32).eps)
+_DBL_MAX = float(np.finfo(np.float64).max)
+# what a path did that the device kernels do not: any of these makes the triple DEGENERATE
+F_DROP_FOR_GOOD, F_ALPHA_UP, F_AA, F_MULTI_DROP, F_KNOTS, F_XROUTE, F_ORDER = 1, 2, 4, 8, 16, 32, 64
+
+
+def lasar_knot_capacity(N):
+    """Knots of one path the device stores (LS_KCAP of csrc/rc_lasar.h): N additions, a few drop / re-add pairs."""
+    return 2 * int(N) + 4
+
+
+def _min_pos(v):
+    v = v[v > 0]
+    return float(v.min()) if v.size else _DBL_MAX
+
+
+def _rotg(a, b):
+    """BLAS rotg: (r, c, s) with [c s; -s c] [a; b] = [r; 0]."""
+    roe = a if abs(a) > abs(b) else b
+    scale = abs(a) + abs(b)
+    if scale == 0.0:
+        return 0.0, 1.0, 0.0
+    r = scale * np.sqrt((a / scale) ** 2 + (b / scale) ** 2)
+    if roe < 0.0:
+        r = -r
+    return r, a / r, b / r
+
+
+def _cholesky_delete(L, n, go_out):
+    """sklearn.utils.arrayfuncs.cholesky_delete on the leading n x n lower factor: remove row / column go_out."""
+    for i in range(go_out, n - 1):
+        L[i, :i + 2] = L[i + 1, :i + 2]
+    for i in range(go_out, n - 1):
+        r, c, s = _rotg(L[i, i], L[i, i + 1])
+        if r < 0.0:
+            r, c, s = -r, -c, -s
+        L[i, i], L[i, i + 1] = r, 0.0
+        for k in range(i + 1, n - 1):
+            xk, yk = L[k, i], L[k, i + 1]
+            L[k, i], L[k, i + 1] = c * xk + s * yk, c * yk - s * xk
+
+
+def _chol_solve(L, n, b):
+    """x with L L^T x = b (lower factor, leading n x n)."""
+    w = np.empty(n)
+    for i in range(n):
+        w[i] = (b[i] - np.dot(L[i, :i], w[:i])) / L[i, i]
+    for i in range(n - 1, -1, -1):
+        w[i] = (w[i] - np.dot(L[i + 1:n, i], w[i + 1:n])) / L[i, i]
+    return w
+
+
+def _lars_path(X, y, use_gram, alpha_min=0.0):
+    """sklearn's ``_lars_path_solver(method="lasso", return_path=True, eps=finfo(float).eps, max_iter=500)`` on
+    centred X [n, p], y [n], restated branch by branch.  Returns the knots' alphas [K], their coefficients [K, p]
+    and the F_* flags of what the path went through."""
+    n_samples, p = y.size, X.shape[1]
+    Cov = np.dot(X.T, y)
+    if use_gram:
+        Gram = np.dot(X.T, X)
+        Gram_copy, Cov_copy = Gram.copy(), Cov.copy()
+    else:
+        Gram = None
+        X = X.copy("F")
+    max_features = min(LARS_MAX_ITER, p)
+    alphas, coefs = [0.0], [np.zeros(p)]
+    n_iter = n_active = 0
+    active, indices = [], np.arange(p)
+    sign_active = np.zeros(max_features)
+    L = np.zeros((max_features, max_features))
+    drop = False
+    flags = 0 if use_gram else F_XROUTE
+    while True:
+        if Cov.size:
+            C_idx = int(np.argmax(np.abs(Cov)))
+            C_ = Cov[C_idx]
+            C = np.fabs(C_)
+        else:
+            C = 0.0
+        coef = coefs[n_iter]
+        prev_alpha = alphas[n_iter - 1]
+        prev_coef = coefs[n_iter - 1]
+        alpha = C / n_samples
+        alphas[n_iter] = alpha
+        if alpha <= alpha_min + _EQ_TOL:   # early stopping
+            if abs(alpha - alpha_min) > _EQ_TOL:
+                if n_iter > 0:
+                    ss = (prev_alpha - alpha_min) / (prev_alpha - alpha)
+                    coef[:] = prev_coef + ss * (coef - prev_coef)
+                alphas[n_iter] = alpha_min
+            break
+        if n_iter >= LARS_MAX_ITER or n_active >= p:
+            break
+        if not drop:
+            sign_active[n_active] = np.sign(C_)
+            m, n = n_active, C_idx + n_active
+            Cov[C_idx], Cov[0] = Cov[0], Cov[C_idx]
+            indices[n], indices[m] = indices[m], indices[n]
+            Cov_not_shortened = Cov
+            Cov = Cov[1:]
+            if Gram is None:
+                tmp = X[:, n].copy()
+                X[:, n] = X[:, m]
+                X[:, m] = tmp
+                c = np.sqrt(np.dot(X[:, n_active], X[:, n_active])) ** 2
+                L[n_active, :n_active] = np.dot(X.T[n_active], X.T[:n_active].T)
+            else:
+                Gram[[m, n]] = Gram[[n, m]]
+                Gram[:, [m, n]] = Gram[:, [n, m]]
+                c = Gram[n_active, n_active]
+                L[n_active, :n_active] = Gram[n_active, :n_active]
+            for i in range(n_active):   # L[:n_active, :n_active] w = L[n_active, :n_active]
+                L[n_active, i] = (L[n_active, i] - np.dot(L[i, :i], L[n_active, :i])) / L[i, i]
+            v = np.dot(L[n_active, :n_active], L[n_active, :n_active])
+            diag = max(np.sqrt(np.abs(c - v)), _EPS)
+            L[n_active, n_active] = diag
+            if diag < 1e-7:   # degenerate regressor: drop it for good
+                flags |= F_DROP_FOR_GOOD
+                Cov = Cov_not_shortened
+                Cov[0] = 0
+                Cov[C_idx], Cov[0] = Cov[0], Cov[C_idx]
+                continue
+            active.append(int(indices[n_active]))
+            n_active += 1
+        if n_iter > 0 and prev_alpha < alpha:   # alpha is increasing: bail out
+            flags |= F_ALPHA_UP
+            break
+        sa = sign_active[:n_active]
+        least_squares = _chol_solve(L, n_active, sa)
+        if least_squares.size == 1 and least_squares[0] == 0:
+            least_squares[...] = 1
+            AA = 1.0
+        else:
+            with np.errstate(all="ignore"):
+                AA = 1.0 / np.sqrt(np.sum(least_squares * sa))
+            if not np.isfinite(AA):   # L is too ill-conditioned
+                flags |= F_AA
+                i = 0
+                L_ = L[:n_active, :n_active].copy()
+                while not np.isfinite(AA):
+                    L_.flat[::n_active + 1] += (2 ** i) * _EPS
+                    least_squares = _chol_solve(L_, n_active, sa)
+                    AA = 1.0 / np.sqrt(max(np.sum(least_squares * sa), _EPS))
+                    i += 1
+            least_squares *= AA
+        if Gram is None:
+            eq_dir = np.dot(X.T[:n_active].T, least_squares)
+            corr_eq_dir = np.dot(X.T[n_active:], eq_dir)
+        else:
+            corr_eq_dir = np.dot(Gram[:n_active, n_active:].T, least_squares)
+        np.around(corr_eq_dir, decimals=15, out=corr_eq_dir)
+        g1 = _min_pos((C - Cov) / (AA - corr_eq_dir + _TINY32))
+        g2 = _min_pos((C + Cov) / (AA + corr_eq_dir + _TINY32))
+        gamma_ = min(g1, g2, C / AA)
+        drop = False
+        z = -coef[active] / (least_squares + _TINY32)
+        z_pos = _min_pos(z)
+        if z_pos < gamma_:   # some coefficients have changed sign
+            idx = np.where(z == z_pos)[0][::-1]
+            if idx.size > 1:
+                flags |= F_MULTI_DROP
+            sign_active[idx] = -sign_active[idx]
+            gamma_ = z_pos
+            drop = True
+        n_iter += 1
+        alphas.append(0.0)
+        coefs.append(np.zeros(p))
+        coef, prev_coef = coefs[n_iter], coefs[n_iter - 1]
+        coef[active] = prev_coef[active] + gamma_ * least_squares
+        Cov -= gamma_ * corr_eq_dir
+        if drop:
+            for ii in idx:
+                _cholesky_delete(L, n_active, int(ii))
+            n_active -= 1
+            drop_idx = [active.pop(int(ii)) for ii in idx]
+            if Gram is None:
+                for ii in idx:
+                    for i in range(int(ii), n_active):
+                        tmp = X[:, i].copy()
+                        X[:, i] = X[:, i + 1]
+                        X[:, i + 1] = tmp
+                        indices[i], indices[i + 1] = indices[i + 1], indices[i]
+                residual = y - np.dot(X[:, :n_active], coef[active])
+                temp = np.atleast_1d(np.dot(X.T[n_active], residual))
+            else:
+                for ii in idx:
+                    for i in range(int(ii), n_active):
+                        indices[i], indices[i + 1] = indices[i + 1], indices[i]
+                        Gram[[i, i + 1]] = Gram[[i + 1, i]]
+                        Gram[:, [i, i + 1]] = Gram[:, [i + 1, i]]
+                temp = Cov_copy[drop_idx] - np.dot(Gram_copy[drop_idx], coef)
+            Cov = np.r_[temp, Cov]
+            sign_active = np.append(np.delete(sign_active, idx), [0.0] * idx.size)
+    if len(alphas) > lasar_knot_capacity(p):
+        flags |= F_KNOTS
+    if not flags and np.any(np.diff(alphas) > 0):   # the last knot's alpha above its predecessor's, without a bail-out
+        flags |= F_ORDER
+    return np.array(alphas), np.array(coefs), flags
+
+
+def _interp_rows(x, y, x_new):
+    """scipy's ``interp1d(x, y, axis=0)(x_new)`` (linear, x sorted first), operation by operation."""
+    ind = np.argsort(x, kind="mergesort")
+    x, y = x[ind], y[ind]
+    hi = np.searchsorted(x, x_new).clip(1, len(x) - 1).astype(int)
+    lo = hi - 1
+    with np.errstate(all="ignore"):
+        slope = (y[hi] - y[lo]) / (x[hi] - x[lo])[:, None]
+        return slope * (x_new - x[lo])[:, None] + y[lo]
+
+
+def _fold_bounds(count, cv):
+    """KFold(cv) without shuffling: contiguous runs, the first count % cv one row longer."""
+    sizes = np.full(cv, count // cv, dtype=np.int64)
+    sizes[:count % cv] += 1
+    ends = np.cumsum(sizes)
+    return ends - sizes, ends
+
+
+def _lasso_lars_cv(X, y, cv):
+    """``LassoLarsCV(cv=cv).fit(X, y)``: (coef_, intercept_, best_alpha, its index in cv_alphas_, flags)."""
+    n, p = X.shape
+    X = X.copy("F" if X.flags["F_CONTIGUOUS"] else "C")
+    y = y.copy()
+    starts, ends = _fold_bounds(n, cv)
+    paths, flags = [], 0
+    for f in range(cv):
+        test = np.arange(starts[f], ends[f])
+        train = np.concatenate([np.arange(0, starts[f]), np.arange(ends[f], n)])
+        Xtr, ytr, Xte, yte = X[train], y[train], X[test], y[test]
+        X_mean = Xtr.mean(axis=0)
+        Xtr -= X_mean
+        Xte -= X_mean
+        y_mean = ytr.mean(axis=0)
+        ytr -= y_mean
+        yte -= y_mean
+        alphas, coefs, fl = _lars_path(Xtr, ytr, Xtr.shape[0] > p)
+        flags |= fl
+        paths.append((alphas, (np.dot(Xte, coefs.T) - yte[:, np.newaxis]).T))
+    all_alphas = np.unique(np.concatenate([a for a, _ in paths]))
+    stride = int(max(1, int(len(all_alphas) / float(LARS_MAX_N_ALPHAS))))
+    all_alphas = all_alphas[::stride]
+    mse_path = np.empty((len(all_alphas), cv))
+    for index, (alphas, residues) in enumerate(paths):
+        alphas, residues = alphas[::-1], residues[::-1]
+        if alphas[0] != 0:
+            alphas = np.r_[0, alphas]
+            residues = np.r_[residues[0, np.newaxis], residues]
+        if alphas[-1] != all_alphas[-1]:
+            alphas = np.r_[alphas, all_alphas[-1]]
+            residues = np.r_[residues, residues[-1, np.newaxis]]
+        this_residues = _interp_rows(alphas, residues, all_alphas)
+        this_residues **= 2
+        mse_path[:, index] = np.mean(this_residues, axis=-1)
+    mask = np.all(np.isfinite(mse_path), axis=-1)
+    all_alphas, mse_path = all_alphas[mask], mse_path[mask]
+    i_best = int(np.argmin(mse_path.mean(axis=-1)))
+    best_alpha = float(all_alphas[i_best])
+    X_offset, y_offset = X.mean(axis=0), y.mean(axis=0)
+    Xc, yc = X - X_offset, y - y_offset
+    alphas, coefs, fl = _lars_path(Xc, yc, n > p, best_alpha)
+    coef = coefs[-1]
+    return coef, y_offset - np.dot(X_offset, coef), best_alpha, i_best, flags | fl
+
+
+def _lasar_stack(x, lags):
+    """Y [n, N] and Z [n, lags N] built with lassovar's own operations (so the memory layouts are its too)."""
+    Y = x.T[:, lags:]
+    Z = np.vstack([x.T[:, lags - k:-k] for k in range(1, lags + 1)])
+    return Y.T, Z.T
+
+
+def _lasar_host_triple(Y, Z, j, lags, cv):
+    """One target of ``lassovar``: (row of scores [lags N], selected [lags N], best_alpha [lags], best index [lags],
+    status, pivot ratio, flags)."""
+    d = Y.shape[1]
+    target = np.copy(Y[:, j])
+    selected = np.full(d * lags, False)
+    best_alpha, best_idx, flags = np.zeros(lags), np.zeros(lags, dtype=np.int32), 0
+    for lag in range(lags):
+        blk = Z[:, d * lag:d * (lag + 1)]
+        coef, intercept, best_alpha[lag], best_idx[lag], fl = _lasso_lars_cv(blk, target, cv)
+        flags |= fl
+        selected[d * lag:d * (lag + 1)] = coef > 0
+        target -= np.dot(blk, coef) + intercept
+    row = np.zeros(d * lags)
+    status, ratio = OK, np.inf
+    if selected.any():
+        ZZ = Z[:, selected]
+        G, r = ZZ.T.dot(ZZ), ZZ.T.dot(Y[:, j])
+        B, ratio, status = _solve_spd(G, r)
+        if status == NONFINITE:
+            raise RuntimeError("lasar: non-finite Gram matrix in a refit")
+        if status == SINGULAR:
+            B = np.linalg.lstsq(G, r, rcond=None)[0]
+        row[selected] = B
+    if flags:
+        status = DEGENERATE
+    return row, selected, best_alpha, best_idx, status, ratio, flags
+
+
+def _lasar_plan(P, T, N, maxlags, n_subsamples, subsample_sizes, cv):
+    n = T - maxlags
+    sizes = list(subsample_sizes)
+    ks = [int(np.round(s * T)) for s in sizes] if n_subsamples else []
+    if min([n] + ks) < cv:   # sklearn: "Cannot have number of splits n_splits greater than the number of samples"
+        raise ValueError("Cannot have number of splits n_splits=%d greater than the number of samples: n_samples=%d."
+                         % (cv, min([n] + ks)))
+    plan = _Plan(_SLARAC, P, 1 + n_subsamples, T, N, maxlags, max([n] + ks))
+    for b in range(P):
+        plan.count[b, 0] = -1
+        for s, size in enumerate(np.random.choice(sizes, n_subsamples)):
+            k = int(np.round(size * T))
+            plan.idx[b, s + 1, :k] = np.random.randint(0, n, size=(k,))
+            plan.count[b, s + 1] = k
+    return plan
+
+
+def lasar_device_supported(T, N, lags):
+    """True when the library's LASAR kernels cover this shape (redcliff_lasar_supported)."""
+    from . import _native
+    return bool(_native.lib().redcliff_lasar_supported(int(T), int(N), int(lags)))
+
+
+def _lasar_route(T, N, lags):
+    forced = os.environ.get("REDCLIFF_TIDYBENCH_PATH", "") or "auto"
+    if forced not in ("auto", "host", "fused"):
+        raise ValueError("REDCLIFF_TIDYBENCH_PATH must be fused, host or auto")
+    if forced == "host":
+        return "host"
+    import torch
+    try:
+        fused = torch.cuda.is_available() and lasar_device_supported(T, N, lags)
+    except ImportError:
+        if forced == "fused":
+            raise
+        fused = False
+    if forced == "fused" and not fused:
+        raise RuntimeError("REDCLIFF_TIDYBENCH_PATH=fused: no GPU, or shape outside redcliff_lasar_supported "
+                           "(T=%d N=%d lags=%d)" % (T, N, lags))
+    return "fused" if fused else "host"
+
+
+def _lasar_groups(L, plan, cv, budget):
+    """[(s0, s1, max_count)]: consecutive fits whose workspace fits the budget (at least one fit per group)."""
+    eff = plan.eff_count().max(axis=0)
+    groups, s0 = [], 0
+    while s0 < plan.S:
+        s1, mc = s0 + 1, int(eff[s0])
+        while s1 < plan.S:
+            m2 = max(mc, int(eff[s1]))
+            if int(L.redcliff_lasar_ws_bytes(plan.P, s1 + 1 - s0, plan.N, plan.lags, cv, m2)) > budget:
+                break
+            s1, mc = s1 + 1, m2
+        groups.append((s0, s1, mc))
+        s0 = s1
+    return groups
+
+
+def _lasar_device(x, dev_data, plan, cv, device, times):
+    import ctypes
+
+    import torch
+
+    from . import _native as nat
+    L = nat.lib()
+    dev = torch.device(device if device is not None else (dev_data.device if dev_data is not None else "cuda"))
+    P, S, N, lags = plan.P, plan.S, plan.N, plan.lags
+    with torch.cuda.device(dev):
+        t0 = time.perf_counter()
+        data = dev_data.to(dev) if dev_data is not None else torch.from_numpy(x).to(dev)
+        idx = torch.from_numpy(plan.idx).to(dev)
+        count = torch.from_numpy(plan.count).to(dev)
+        torch.cuda.synchronize()
+        times["upload"] += time.perf_counter() - t0
+        shapes = (("coef", (P, S, N, N), torch.float64), ("best_alpha", (P, S, N), torch.float64),
+                  ("best_index", (P, S, N), torch.int32), ("selected", (P, S, N), torch.int32),
+                  ("status", (P, S, N), torch.int32), ("pivot_ratio", (P, S, N), torch.float64))
+        out = {k: torch.empty(shp, dtype=dt, device=dev) for k, shp, dt in shapes}
+        groups = _lasar_groups(L, plan, cv, int(WORKSPACE_BUDGET_BYTES))
+        nbytes = max(int(L.redcliff_lasar_ws_bytes(P, s1 - s0, N, lags, cv, mc)) for s0, s1, mc in groups)
+        ws = torch.empty((nbytes + 7) // 8, dtype=torch.float64, device=dev)
+        stream = torch.cuda.current_stream().cuda_stream
+        e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+        keep = []
+        e0.record()
+        for s0, s1, mc in groups:
+            one = len(groups) == 1
+            g_count = count if one else count[:, s0:s1].contiguous()
+            g = out if one else {k: torch.empty((P, s1 - s0) + shp[2:], dtype=dt, device=dev) for k, shp, dt in shapes}
+            a = nat.LasarArgs()
+            a.P, a.S, a.T, a.N, a.lags, a.cv, a.max_count = P, s1 - s0, plan.T, N, lags, cv, mc
+            a.data = data.data_ptr()
+            a.idx = idx.data_ptr() + 4 * s0 * idx.stride(1)
+            a.idx_pstride, a.idx_fstride = idx.stride(0), idx.stride(1)
+            a.count = g_count.data_ptr()
+            a.coef, a.best_alpha, a.best_index = g["coef"].data_ptr(), g["best_alpha"].data_ptr(), g["best_index"].data_ptr()
+            a.selected, a.status, a.pivot_ratio = g["selected"].data_ptr(), g["status"].data_ptr(), g["pivot_ratio"].data_ptr()
+            a.ws, a.ws_bytes = ws.data_ptr(), nbytes
+            nat.check(L.redcliff_lasar_run(ctypes.byref(a), ctypes.c_void_p(stream)), "lasar_run")
+            if not one:
+                for k in out:
+                    out[k][:, s0:s1].copy_(g[k])
+            keep.append((g_count, g))
+        e1.record()
+        e1.synchronize()
+        times["kernels"] += e0.elapsed_time(e1) * 1e-3
+        res = {k: v.cpu().numpy() for k, v in out.items()}
+    res["groups"] = len(groups)
+    return res
+
+
+def lasar_many(datas, maxlags=1, n_subsamples=100, subsample_sizes=DEFAULT_SUBSAMPLE_SIZES, cv=5,
+               aggregate_lags=_max_over_lags, device=None, return_info=False, **kwargs):
+    """LASAR scores [P, N, N] of P same-shape series [P, T, N] in one native call.  The draws are made problem by
+    problem, so under one seed the result equals a loop of ``lasar`` calls."""
+    proc = _pop_processing(kwargs)
+    if kwargs:
+        raise TypeError("unexpected keyword arguments: %s" % sorted(kwargs))
+    times = dict.fromkeys(("draws", "upload", "kernels", "fallback", "aggregate"), 0.0)
+    t_all = time.perf_counter()
+    x, dev_data = _host_series(datas, proc, None)
+    P, T, N = x.shape
+    lags, cv, S = int(maxlags), int(cv), 1 + int(n_subsamples)
+    if lags < 1 or T <= lags:
+        raise ValueError("need 1 <= maxlags < T (maxlags=%d, T=%d)" % (lags, T))
+    if cv < 2:
+        raise ValueError("cv must be at least 2")
+    route = _lasar_route(T, N, lags)
+    t0 = time.perf_counter()
+    plan = _lasar_plan(P, T, N, lags, int(n_subsamples), subsample_sizes, cv)
+    times["draws"] = time.perf_counter() - t0
+    D = lags * N
+    coef = np.zeros((P, S, N, D))
+    selected = np.zeros((P, S, N, D), dtype=bool)
+    best_alpha = np.zeros((P, S, N, lags))
+    best_index = np.zeros((P, S, N, lags), dtype=np.int32)
+    status = np.zeros((P, S, N), dtype=np.int32)
+    ratio = np.full((P, S, N), np.inf)
+    flags = np.zeros((P, S, N), dtype=np.int32)
+    groups = 1
+    if route == "fused":
+        res = _lasar_device(x, dev_data, plan, cv, device, times)
+        groups = res["groups"]
+        if (res["status"] == NONFINITE).any():
+            raise RuntimeError("lasar: %d target(s) ended NONFINITE on the device" % int((res["status"] == NONFINITE).sum()))
+        coef[:], status[:], ratio[:] = res["coef"], res["status"], res["pivot_ratio"]
+        best_alpha[..., 0], best_index[..., 0] = res["best_alpha"], res["best_index"]
+        selected[:] = (res["selected"][..., None] >> np.arange(N)) & 1
+        todo = np.argwhere((status == SINGULAR) | (status == DEGENERATE))
+    else:
+        todo = np.argwhere(np.ones((P, S), dtype=bool))
+    t0 = time.perf_counter()
+    stacks = {}
+    for t in todo:
+        b, s = int(t[0]), int(t[1])
+        if (b, s) not in stacks:
+            if route == "fused":
+                stacks.clear()
+            Y, Z = _lasar_stack(x[b], lags)
+            rows = plan.rows(b, s)
+            stacks[(b, s)] = (Y, Z) if rows is None else (Y[rows], Z[rows])
+        Y, Z = stacks[(b, s)]
+        for j in ([int(t[2])] if route == "fused" else range(N)):
+            (coef[b, s, j], selected[b, s, j], best_alpha[b, s, j], best_index[b, s, j], st, ratio[b, s, j],
+             flags[b, s, j]) = _lasar_host_triple(Y, Z, j, lags, cv)
+            if route == "host":
+                status[b, s, j] = st
+        if route == "host":
+            stacks.clear()
+    times["fallback" if route == "fused" else "kernels"] += time.perf_counter() - t0
+    t0 = time.perf_counter()
+    scores = []
+    for b in range(P):
+        tot = np.abs(coef[b, 0])
+        for s in range(1, S):
+            tot += np.abs(coef[b, s])
+        tot /= S
+        scores.append(_post(aggregate_lags(tot.reshape(N, -1, N)), proc))
+    scores = np.stack(scores)
+    times["aggregate"] = time.perf_counter() - t0
+    times["total"] = time.perf_counter() - t_all
+    info = {"route": route, "status": status, "pivot_ratio": ratio, "time": times, "coef": coef, "groups": groups,
+            "n_host_solved": int(len(todo)) if route == "fused" else 0, "count": plan.count.copy(), "selected": selected,
+            "best_alpha": best_alpha, "best_index": best_index, "flags": flags}
+    return (scores, info) if return_info else scores
+
+
+def lasar(data, maxlags=1, n_subsamples=100, subsample_sizes=DEFAULT_SUBSAMPLE_SIZES, cv=5, aggregate_lags=_max_over_lags,
+          **kwargs):
+    """LASAR (LASso Auto-Regression): data [T, N] -> scores [N, N], entry (i, j) for the link X_i -> X_j.  The
+    reference's signature and processing keywords; see ``slarac``.  Per target a cross-validated lasso path
+    (sklearn's ``LassoLarsCV``) selects the parents with a positive coefficient, a least-squares refit on them gives
+    the scores, averaged in absolute value over the full series and ``n_subsamples`` bootstrap subsamples."""
+    if len(getattr(data, "shape", ())) != 2:
+        data = np.asarray(data)
+    if len(data.shape) != 2:
+        raise ValueError("data must be [T, N]")
+    out = lasar_many(data[None], maxlags=maxlags, n_subsamples=n_subsamples, subsample_sizes=subsample_sizes, cv=cv,
+                     aggregate_lags=aggregate_lags, **kwargs)
+    if not kwargs.get("return_info", False):
+        return out[0]
+    d = dict(out[1])
+    for k in ("status", "pivot_ratio", "coef", "count", "selected", "best_alpha", "best_index", "flags"):
+        d[k] = d[k][0]
+    return out[0][0], d
+
+
+def run_lasar_experiment(samples):
+    """Regime-aware LASAR as the evaluation scripts run it: one score matrix per regime from the series masked to
+    that regime's rows, ``post_standardise=True``, |.| with a zero diagonal; the R masked series go through one
+    ``lasar_many`` call."""
+    data, _, masks, _, _, _, R = prepare_data_for_modeling(samples)
+    scores = lasar_many(np.stack([data * masks[r] for r in range(R)]), post_standardise=True)
     return [get_standardized_off_diagonal_relation_predictions(scores[r], transpose=False) for r in range(R)]
