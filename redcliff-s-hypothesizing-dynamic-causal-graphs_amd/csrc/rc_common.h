@@ -567,32 +567,33 @@ __device__ inline void rc_stage(int N, Ld ld, St st) {
 
 // Several staging segments with all their loads in flight together: round r issues the
 // loads of elements [r*U*256, (r+1)*U*256) of EVERY segment, then stores them.  A segment
-// is rc_seg<U>(N, ld, st); U is its loads per thread per round.
-template <int U, class Ld, class St>
+// is rc_seg<U>(N, ld, st); U is its loads per thread per round.  NT (here and in the segments below):
+// the workgroup's threads, RC_BLOCK unless the kernel launches another size (rc_seg<U, NT>).
+template <int U, int NT, class Ld, class St>
 struct RcSeg {
   int N;
   Ld ld;
   St st;
   float v[U];
-  __device__ inline bool active(int r) const { return r * U * RC_BLOCK < N; }
+  __device__ inline bool active(int r) const { return r * U * NT < N; }
   __device__ inline void load(int r) {
 #pragma unroll
     for (int u = 0; u < U; ++u) {
-      const int e = r * U * RC_BLOCK + u * RC_BLOCK + (int)threadIdx.x;
+      const int e = r * U * NT + u * NT + (int)threadIdx.x;
       v[u] = e < N ? ld(e) : 0.f;
     }
   }
   __device__ inline void store(int r) {
 #pragma unroll
     for (int u = 0; u < U; ++u) {
-      const int e = r * U * RC_BLOCK + u * RC_BLOCK + (int)threadIdx.x;
+      const int e = r * U * NT + u * NT + (int)threadIdx.x;
       if (e < N) st(e, v[u]);
     }
   }
 };
-template <int U, class Ld, class St>
-__device__ inline RcSeg<U, Ld, St> rc_seg(int N, Ld ld, St st) {
-  return RcSeg<U, Ld, St>{N, ld, st, {}};
+template <int U, int NT = RC_BLOCK, class Ld, class St>
+__device__ inline RcSeg<U, NT, Ld, St> rc_seg(int N, Ld ld, St st) {
+  return RcSeg<U, NT, Ld, St>{N, ld, st, {}};
 }
 template <class... S>
 __device__ inline void rc_stage_all(S&&... s) {
@@ -605,31 +606,31 @@ __device__ inline void rc_stage_all(S&&... s) {
 // A segment whose ld(e) is valid for every e in [0, N): the loads carry no per-lane guard (a guarded
 // load is an exec-mask branch per element).  Whole groups of RC_BLOCK elements past N are skipped
 // by a uniform (scalar) test, the lanes past N of the last group load element N - 1 and store nothing.
-template <int U, class Ld, class St>
+template <int U, int NT, class Ld, class St>
 struct RcSegC {
   int N;
   Ld ld;
   St st;
   float v[U];
-  __device__ inline bool active(int r) const { return r * U * RC_BLOCK < N; }
+  __device__ inline bool active(int r) const { return r * U * NT < N; }
   __device__ inline void load(int r) {
 #pragma unroll
     for (int u = 0; u < U; ++u) {
-      const int e0 = (r * U + u) * RC_BLOCK;
+      const int e0 = (r * U + u) * NT;
       if (e0 < N) v[u] = ld(min(e0 + (int)threadIdx.x, N - 1));
     }
   }
   __device__ inline void store(int r) {
 #pragma unroll
     for (int u = 0; u < U; ++u) {
-      const int e0 = (r * U + u) * RC_BLOCK, e = e0 + (int)threadIdx.x;
+      const int e0 = (r * U + u) * NT, e = e0 + (int)threadIdx.x;
       if (e0 < N && e < N) st(e, v[u]);
     }
   }
 };
-template <int U, class Ld, class St>
-__device__ inline RcSegC<U, Ld, St> rc_segc(int N, Ld ld, St st) {
-  return RcSegC<U, Ld, St>{N, ld, st};
+template <int U, int NT = RC_BLOCK, class Ld, class St>
+__device__ inline RcSegC<U, NT, Ld, St> rc_segc(int N, Ld ld, St st) {
+  return RcSegC<U, NT, Ld, St>{N, ld, st};
 }
 
 // The lag windows of a tile of batch rows, as the factor kernels stage them: tile[b][q], q = ch L + t,
@@ -652,20 +653,20 @@ __device__ __forceinline__ RcWin rc_win(const StepCtx& c, const float* X, int b0
   return RcWin{X + ((c.row0 + b0) * d.T + (c.Lmax - d.L)) * d.p, d.T * d.p, d.p, d.L, d.p * d.L,
                c.mg[RC_MG_Q], c.mg[RC_MG_P], c.mg[RC_MG_L]};
 }
-template <int U, int TWL>
+template <int U, int TWL, int NT>
 struct RcWinSeg {
   RcWin w;
   int N, nb, q0, stride, padto;
   bool slab;
   float* tile;
   float v[U];
-  __device__ __forceinline__ bool active(int r) const { return r * U * RC_BLOCK < N; }
+  __device__ __forceinline__ bool active(int r) const { return r * U * NT < N; }
   __device__ __forceinline__ void load(int r) {
     if (slab) {
       const RcDiv32 dQ(w.Q, w.mQ);
 #pragma unroll
       for (int u = 0; u < U; ++u) {
-        const int e0 = (r * U + u) * RC_BLOCK;
+        const int e0 = (r * U + u) * NT;
         if (e0 < N) {
           const int e = min(e0 + (int)threadIdx.x, N - 1), b = dQ.div(e);
           v[u] = w.base[(unsigned)(e + b * (w.Tp - w.Q))];
@@ -675,7 +676,7 @@ struct RcWinSeg {
       const RcDiv32 dL(w.L, w.mL);
 #pragma unroll
       for (int u = 0; u < U; ++u) {
-        const int e0 = (r * U + u) * RC_BLOCK;
+        const int e0 = (r * U + u) * NT;
         if (e0 < N) {
           const int e = min(e0 + (int)threadIdx.x, N - 1), b = e >> TWL, q = q0 + (e & ((1 << TWL) - 1));
           const bool in = q < w.Q;
@@ -691,7 +692,7 @@ struct RcWinSeg {
       const RcDiv32 dQ(w.Q, w.mQ), dp(w.p, w.mp);
 #pragma unroll
       for (int u = 0; u < U; ++u) {
-        const int e0 = (r * U + u) * RC_BLOCK, e = e0 + (int)threadIdx.x;
+        const int e0 = (r * U + u) * NT, e = e0 + (int)threadIdx.x;
         if (e0 < N && e < N) {
           const int b = dQ.div(e), s = e - b * w.Q, t = dp.div(s), ch = s - t * w.p;
           tile[b * stride + ch * w.L + t] = v[u];
@@ -701,12 +702,12 @@ struct RcWinSeg {
       if (r == 0 && pw > 0 && N > 0) {
         const int sh = pw <= 16 ? 4 : (pw <= 32 ? 5 : 6), col = (int)threadIdx.x & ((1 << sh) - 1);
         if (col < pw)
-          for (int b = (int)threadIdx.x >> sh; b < nb; b += RC_BLOCK >> sh) tile[b * stride + w.Q + col] = 0.f;
+          for (int b = (int)threadIdx.x >> sh; b < nb; b += NT >> sh) tile[b * stride + w.Q + col] = 0.f;
       }
     } else {
 #pragma unroll
       for (int u = 0; u < U; ++u) {
-        const int e0 = (r * U + u) * RC_BLOCK, e = e0 + (int)threadIdx.x;
+        const int e0 = (r * U + u) * NT, e = e0 + (int)threadIdx.x;
         if (e0 < N && e < N) tile[(e >> TWL) * stride + (e & ((1 << TWL) - 1))] = v[u];
       }
     }
@@ -714,9 +715,9 @@ struct RcWinSeg {
 };
 // rows [0, nb) of the tile at `tile` (row stride `stride`); slab: the whole window (q0 == 0, Q columns,
 // zeros up to padto), else columns [q0, q0 + (1 << TWL)).  nb == 0: an empty segment.
-template <int U, int TWL>
-__device__ __forceinline__ RcWinSeg<U, TWL> rc_win_seg(const RcWin w, bool slab, int nb, int q0, float* tile, int stride, int padto) {
-  RcWinSeg<U, TWL> s;
+template <int U, int TWL, int NT = RC_BLOCK>
+__device__ __forceinline__ RcWinSeg<U, TWL, NT> rc_win_seg(const RcWin w, bool slab, int nb, int q0, float* tile, int stride, int padto) {
+  RcWinSeg<U, TWL, NT> s;
   s.w = w;
   s.N = slab ? nb * w.Q : nb << TWL;
   s.nb = nb; s.q0 = q0; s.stride = stride; s.padto = padto;

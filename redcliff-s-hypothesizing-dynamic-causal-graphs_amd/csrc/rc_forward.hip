@@ -14,6 +14,7 @@
 // and models/cmlp.py:12-35 / :90-101 (MLP: Conv1d(p, h, L) -> ReLU -> Conv1d(h, 1, 1)),
 // models/cmlp.py:147-167 (group norms of layer-0 weights, pre-update).
 #include <cstdlib>
+#include <cstring>
 #include <type_traits>
 
 #include "rc_common.h"
@@ -22,6 +23,10 @@ namespace {
 
 #define FK_BT 128  // windows per factor-forward tile (16 row groups x 8)
 #define FQ_MAX 96  // layer-0 contraction staged in one pass up to this length
+#define RC_EMB_TEAM_NT 512  // the wave-team workgroup: two teams of four waves (emb_fwd_body)
+#ifndef FF_KB
+#define FF_KB 4  // k-steps per operand batch of the factor forward's chains (rc_fac_bwd.h's FB_KB)
+#endif
 
 __device__ inline int fq_tile(const RedcliffDims& d) { return d.p * d.L <= FQ_MAX ? d.p * d.L : 32; }
 
@@ -36,8 +41,14 @@ __device__ inline int fq_tile(const RedcliffDims& d) { return d.p * d.L <= FQ_MA
 // convolution and fc1 columns of its channels -- stores its fc1 partials write-through and counts
 // itself in on the window's arrival counter; the workgroup that arrives last sums the partials in
 // slice order and runs fc2.  No workgroup waits for another.
-template <int NBT>
+// NT = RC_EMB_TEAM_NT (512 threads, one window, Zs <= 2, zs < 0): wave team t (waves 4t .. 4t+3) runs
+// slice t's fc1 with the lane chains of a 256-thread workgroup's four waves, the row-holding lanes
+// leave the slice sums in LDS and f1 = (part_0 + part_1) + fc1b after one barrier -- the order of
+// both other paths, without the store / drain / counter / reload exchange between workgroups.
+template <int NBT, int NT>
 __device__ __attribute__((always_inline)) void emb_fwd_body(const StepCtx& c, int bx, int SB, int w_lds, int cs, int zs, float* sm) {
+  constexpr bool TEAM = NT == RC_EMB_TEAM_NT;
+  constexpr int UD = NT / RC_BLOCK;  // staging loads per thread shrink with the block
   const RedcliffDims& d = c.d;
   const int r = rc_rep(c, blockIdx.y);
   const int b0 = bx * SB;
@@ -67,10 +78,11 @@ __device__ __attribute__((always_inline)) void emb_fwd_body(const StepCtx& c, in
   float* fb2 = fb1 + M1;               // [K]
   float* alpha = fb2 + K;              // [F]
   float* beta = alpha + F;             // [F]
+  float* partl = beta + F;             // [2][M1]      wave teams' fc1 slice sums (TEAM)
 
   if (blockIdx.x == 0) {  // arrival counters of the embedder backward (they also self-reset)
     unsigned* cnt = reinterpret_cast<unsigned*>(ws + c.wo.ecnt);
-    for (int e = tid; e < p * rc_nchunk(d); e += RC_BLOCK) cnt[e] = 0u;
+    for (int e = tid; e < p * rc_nchunk(d); e += NT) cnt[e] = 0u;
   }
   // BatchNorm statistics (torch forms the scale in double in train mode), issued first
   RC_PHASE(c.ws, c.wo.total, bx, 1);
@@ -94,18 +106,18 @@ __device__ __attribute__((always_inline)) void emb_fwd_body(const StepCtx& c, in
   // round is another memory latency on every workgroup's path): n p^2 <= 512 (C1(K=4) 300, TST 432),
   // n F H <= 5,120 (4,800), K M1 <= 1,024 (TST 576)
   rc_stage_all(
-      rc_seg<2>(n * p * p, [&](int e) { return S[e]; }, [&](int e, float v) { Sl[e] = v; }),
-      rc_seg<20>(w_lds ? nFH : 0, [&](int e) { return gw[e]; }, [&](int e, float v) { Wl[e] = v; }),
+      rc_seg<2 / UD, NT>(n * p * p, [&](int e) { return S[e]; }, [&](int e, float v) { Sl[e] = v; }),
+      rc_seg<20 / UD, NT>(w_lds ? nFH : 0, [&](int e) { return gw[e]; }, [&](int e, float v) { Wl[e] = v; }),
       // window rows are contiguous in the channel index: read (s, f, ch), store [s][ch][f]
-      rc_seg<4>(nb * pF, [&](int e) {
+      rc_seg<4 / UD, NT>(nb * pF, [&](int e) {
         const int s = dpF.div(e), rem = e - s * pF;
         return X[(c.row0 + b0 + s) * d.T * p + (int64_t)(c.Lmax - F) * p + rem];
       }, [&](int e, float v) {
         const int s = dpF.div(e), rem = e - s * pF, f = dp.div(rem), ch = rem - f * p;
         xs[s * pF + ch * F + f] = v;
       }),
-      rc_seg<4>(K * M1, [&](int e) { return E[c.eo.fc2W + e]; }, [&](int e, float v) { fc2s[e] = v; }),
-      rc_seg<1>(M1 + K, [&](int e) { return e < M1 ? E[c.eo.fc1b + e] : E[c.eo.fc2b + e - M1]; },
+      rc_seg<4 / UD, NT>(K * M1, [&](int e) { return E[c.eo.fc2W + e]; }, [&](int e, float v) { fc2s[e] = v; }),
+      rc_seg<1, NT>(M1 + K, [&](int e) { return e < M1 ? E[c.eo.fc1b + e] : E[c.eo.fc2b + e - M1]; },
                 [&](int e, float v) { fb1[e] = v; }));  // fb2 follows fb1
   RC_PHASE(c.ws, c.wo.total, bx, 2);
   if (tid < F) {
@@ -118,7 +130,7 @@ __device__ __attribute__((always_inline)) void emb_fwd_body(const StepCtx& c, in
     beta[tid] = bb - mean * a;
   }
   __syncthreads();
-  for (int e = tid; e < nb * pF; e += RC_BLOCK) {
+  for (int e = tid; e < nb * pF; e += NT) {
     const int f = dF.mod(e);
     xs[e] = xs[e] * alpha[f] + beta[f];
   }
@@ -132,7 +144,7 @@ __device__ __attribute__((always_inline)) void emb_fwd_body(const StepCtx& c, in
   const RcDiv32 dcF = mb >= 0 ? RcDiv32(cF, c.mg[mb]) : (cw == p ? RcDiv32(cF, c.mg[RC_MG_PF]) : RcDiv32(cF));
   const RcDiv32 dncF = mb >= 0 ? RcDiv32(n * cF, c.mg[mb + 1]) : (cw == p ? RcDiv32(n * cF, c.mg[RC_MG_NPF]) : RcDiv32(n * cF));
   const RcDiv32 dcH = mb >= 0 ? RcDiv32(cH, c.mg[mb + 2]) : (cw == p ? RcDiv32(cH, c.mg[RC_MG_PH]) : RcDiv32(cH));
-  for (int e = tid; e < nb * n * cF; e += RC_BLOCK) {
+  for (int e = tid; e < nb * n * cF; e += NT) {
     const int s = dncF.div(e), rs = e - s * n * cF, i = dcF.div(rs), qs = rs - i * cF;
     const int q = ch0 * F + qs, rem = i * pF + q, ch = dF.div(q), f = q - ch * F;
     float v;
@@ -151,7 +163,9 @@ __device__ __attribute__((always_inline)) void emb_fwd_body(const StepCtx& c, in
   RC_PHASE(c.ws, c.wo.total, bx, 4);
   // fc1 weights of the first column step are issued before the graph convolution runs
   const float* W1 = E + c.eo.fc1W;
-  const int lane = tid & 63, wv = __builtin_amdgcn_readfirstlane(tid >> 6);
+  const int lane = tid & 63, wv = __builtin_amdgcn_readfirstlane(tid >> 6) & 3;  // (the wave of its team)
+  const int team = TEAM ? __builtin_amdgcn_readfirstlane(tid >> 8) : 0;
+  const int fz0 = TEAM ? min(team, Zs) : zlo, fz1 = TEAM ? min(team + 1, Zs) : zhi;  // this wave's fc1 slices
   const int RW = (M1 + 3) / 4, m0 = wv * RW;
   // three buffers of column-step weights in rotation (p*H = 1,000 - 1,200 at C1 / TST is 16 - 19
   // column steps): each buffer is refilled right after it is multiplied and read two steps
@@ -159,19 +173,21 @@ __device__ __attribute__((always_inline)) void emb_fwd_body(const StepCtx& c, in
   // Rows past M1 are wave-uniform zeros; a lane past p*H loads a clamped (valid) column that its
   // masked multiply never uses, so no load sits behind a lane-varying condition.
   auto qend = [&](int z) { return min(p, (z + 1) * cs) * H; };  // fc1 columns of slice z: [z*cs*H, qend(z))
-  int qb = qend(zlo);
+  int qb = qend(fz0);
   auto ldw = [&](float (&w)[16], int qn) {
     const int qc = qn < qb ? qn : qb - 1;
 #pragma unroll
     for (int j = 0; j < 16; ++j) w[j] = (j < RW && m0 + j < M1) ? W1[(int64_t)(m0 + j) * pH + qc] : 0.f;
   };
   float wb0[16], wb1[16], wb2[16];
-  ldw(wb0, zlo * cs * H + lane);
-  ldw(wb1, zlo * cs * H + lane + 64);
+  if (fz0 < fz1) {
+    ldw(wb0, fz0 * cs * H + lane);
+    ldw(wb1, fz0 * cs * H + lane + 64);
+  }
   RC_PHASE(c.ws, c.wo.total, bx, 5);
   // Z = sum_i T_i W_i ; R = relu(Z)
   const float* Wsrc = w_lds ? Wl : gw;
-  for (int e = tid; e < nb * cH; e += RC_BLOCK) {
+  for (int e = tid; e < nb * cH; e += NT) {
     const int s = dcH.div(e), rem = ch0 * H + (e - s * cH), ch = dH.div(rem), hh = rem - ch * H;
     float a4[4] = {0.f, 0.f, 0.f, 0.f};  // four independent chains hide the LDS latency
     for (int i = 0; i < n; ++i) {
@@ -198,10 +214,10 @@ __device__ __attribute__((always_inline)) void emb_fwd_body(const StepCtx& c, in
   auto fc1 = [&](auto nbc) {
     constexpr int NB = decltype(nbc)::value;
     float tot[NB];  // row mrow of each window: the slice sums in slice order
-    for (int z = zlo; z < zhi; ++z) {
+    for (int z = fz0; z < fz1; ++z) {
       const int qa = z * cs * H;
       qb = qend(z);
-      if (z > zlo) {  // the first slice's first two column steps were issued before the graph convolution
+      if (z > fz0) {  // the first slice's first two column steps were issued before the graph convolution
         ldw(wb0, qa + lane);
         ldw(wb1, qa + lane + 64);
       }
@@ -255,10 +271,12 @@ __device__ __attribute__((always_inline)) void emb_fwd_body(const StepCtx& c, in
         float t = v[0];
         t += __shfl_xor(t, 2, 64);
         t += __shfl_xor(t, 1, 64);
-        tot[s] = z == zlo ? t : tot[s] + t;
+        tot[s] = z == fz0 ? t : tot[s] + t;
       }
     }
-    if (zs < 0) {  // every slice here: f1 = slice sums + bias
+    if (TEAM) {  // this team's slice sums, exchanged through LDS below
+      if (wrow && fz0 < fz1) partl[team * M1 + mrow] = tot[0];
+    } else if (zs < 0) {  // every slice here: f1 = slice sums + bias
 #pragma unroll
       for (int s = 0; s < NB; ++s) {
         if (s >= nb) break;
@@ -273,7 +291,15 @@ __device__ __attribute__((always_inline)) void emb_fwd_body(const StepCtx& c, in
     }
   };
   fc1(std::integral_constant<int, NBT>{});  // NBT >= SB (k_forward's instantiation for this launch)
-  if (zs >= 0) {  // arrival: the last of the window's Zs workgroups sums the partials and runs fc2
+  if (TEAM) {
+    __syncthreads();
+    RC_PHASE(c.ws, c.wo.total, bx, 12);  // (trace builds: the teams' slice sums are in LDS)
+    if (tid < M1) {
+      const float val = Zs > 1 ? (partl[tid] + partl[M1 + tid]) + fb1[tid] : partl[tid] + fb1[tid];
+      f1l[tid] = val;
+      ws[c.wo.f1 + (int64_t)b0 * M1 + tid] = val;
+    }
+  } else if (zs >= 0) {  // arrival: the last of the window's Zs workgroups sums the partials and runs fc2
     __shared__ unsigned last;
     unsigned* cnt = reinterpret_cast<unsigned*>(ws + c.wo.ecnt) + p * rc_nchunk(d) + 1 + b0;
     asm volatile("s_waitcnt vmcnt(0)" ::: "memory");  // every storing wave drains its partials
@@ -303,7 +329,7 @@ __device__ __attribute__((always_inline)) void emb_fwd_body(const StepCtx& c, in
   }
   __syncthreads();
   RC_PHASE(c.ws, c.wo.total, bx, 7);
-  for (int e = tid; e < nb * K; e += RC_BLOCK) {
+  for (int e = tid; e < nb * K; e += NT) {
     const int s = e / K, k = e - s * K;
     const float* w2 = fc2s + k * M1;
     float a = 0.f;
@@ -314,10 +340,10 @@ __device__ __attribute__((always_inline)) void emb_fwd_body(const StepCtx& c, in
   RC_WG_MARK(c.ws, c.wo.total, RC_KID_EMB_FWD, 1);
 }
 
-size_t emb_fwd_floats(const RedcliffDims& d, int SB, int w_lds) {
+size_t emb_fwd_floats(const RedcliffDims& d, int SB, int w_lds, bool team = false) {
   const size_t pF = (size_t)d.p * d.F, pH = (size_t)d.p * d.H;
   return SB * pF + (size_t)d.n * d.p * d.p + (w_lds ? (size_t)d.n * d.F * d.H : 0) + SB * d.n * pF + SB * pH +
-         (size_t)SB * d.M1 + (size_t)d.K * d.M1 + d.M1 + d.K + 2 * d.F;
+         (size_t)SB * d.M1 + (size_t)d.K * d.M1 + d.M1 + d.K + 2 * d.F + (team ? 2 * d.M1 : 0);
 }
 
 // ------------------------------------------------------------------------------------------
@@ -325,9 +351,17 @@ size_t emb_fwd_floats(const RedcliffDims& d, int SB, int w_lds) {
 // a[kj][b][u], partial outputs y[uc][kj][b] = sum_{u in chunk} W1[u] a[b][u] (+ b1 in chunk
 // 0), the chunk's squared layer-0 group norms gq[uc][kj][q] and a snapshot of W1.
 // The whole window block and weight chunk are staged in one pass when p*L <= FQ_MAX.
+// mfma (slab tiles, Q <= FQ_MAX): the products run on the matrix cores as 16x16x4 chains (rows = the
+// chunk's units, columns = a tile of 16 windows, waves take the window tiles in turn), a k-ascending
+// fmaf chain per output from 0 like the vector loop's and rc_fac_bwd.h's recompute, so the same bits.
+// The tile rows stay QT + 1 wide and unpadded: the reads of the last k-steps are clamped to column
+// Q - 1 and zeros selected (rc_mfma_chain16<., true>).  32-column tiles (Q > FQ_MAX) keep the vector loop.
 // (trace builds: phase marks 64-67 of factor workgroup 0 -- staged, group norms stored, products
-// done, outputs stored)
+// done (wave 0's first chain), outputs stored)
+// MF is a template parameter so that a launch of the vector form carries none of the chains' registers.
+template <int NT, bool MF>
 __device__ __attribute__((always_inline)) void fac_fwd_body(const StepCtx& c, int bx, float* sm) {
+  constexpr int UD = NT / RC_BLOCK, NI = FK_BT * FAC_UC / NT;  // NI: windows per thread of the vector loop
   const RedcliffDims& d = c.d;
   RC_WG_MARK(c.ws, c.wo.total, RC_KID_FAC_FWD, 0);
   const int nU = rc_nuchunk(d);
@@ -351,32 +385,42 @@ __device__ __attribute__((always_inline)) void fac_fwd_body(const StepCtx& c, in
   const int nrow = min(FAC_UC, h - u0);  // the chunk's rows below h: nrow * Q contiguous floats of W0
   const float* W0c = W0 + u0 * Q;        // (32-bit offsets inside the factor slice, as in rc_fac_bwd.h)
   const float bu = u < h ? b0[u] : 0.f, w1 = u < h ? W1[u] : 0.f;
+  // matrix-core form: lane (l15, lg) holds units u0 + 4 lg .. + 3 of window 16 tile + l15
+  const bool mf = MF && slab;
+  const int lane = tid & 63, fwv = __builtin_amdgcn_readfirstlane(tid >> 6), l15 = lane & 15, lg = lane >> 4;
+  float bu4[4], w14[4];
+#pragma unroll
+  for (int reg = 0; reg < 4; ++reg) {
+    const int uu = u0 + 4 * lg + reg;
+    bu4[reg] = mf && uu < h ? b0[uu] : 0.f;
+    w14[reg] = mf && uu < h ? W1[uu] : 0.f;
+  }
 
   for (int bc = 0; bc < c.B; bc += FK_BT) {
-    float acc[8];
+    float acc[NI];
 #pragma unroll
-    for (int i = 0; i < 8; ++i) acc[i] = 0.f;
+    for (int i = 0; i < NI; ++i) acc[i] = 0.f;
     for (int q0 = 0; q0 < Q; q0 += QT) {
       if (q0 > 0 || bc > 0) __syncthreads();
       // (rows past B of the window tile are not staged: their sums are never stored)
       rc_stage_all(
-          rc_win_seg<24, 5>(rc_win(c, X, bc), slab, min(FK_BT, c.B - bc), q0, Xs, QP, Q),
-          rc_segc<4>(slab ? nrow * Q : 0, [&](int e) { return W0c[(unsigned)e]; }, [&](int e, float v) {
+          rc_win_seg<24 / UD, 5, NT>(rc_win(c, X, bc), slab, min(FK_BT, c.B - bc), q0, Xs, QP, Q),
+          rc_segc<4 / UD, NT>(slab ? nrow * Q : 0, [&](int e) { return W0c[(unsigned)e]; }, [&](int e, float v) {
             const int uu = dQ.div(e);
             Ws[uu * QP + e - uu * Q] = v;
           }),
-          rc_segc<2>(slab ? 0 : FAC_UC * 32, [&](int e) {  // 32-column tiles (QT == 32)
+          rc_segc<2 / UD, NT>(slab ? 0 : FAC_UC * 32, [&](int e) {  // 32-column tiles (QT == 32)
             const int uu = e >> 5, q = q0 + (e & 31);
             const bool in = uu < nrow && q < Q;
             const float w = W0c[(unsigned)(in ? uu * Q + q : 0)];
             return in ? w : 0.f;
           }, [&](int e, float v) { Ws[(e >> 5) * QP + (e & 31)] = v; }));
       if (slab)  // a partial chunk: the rows past h are zero
-        for (int e = nrow * QP + tid; e < FAC_UC * QP; e += RC_BLOCK) Ws[e] = 0.f;
+        for (int e = nrow * QP + tid; e < FAC_UC * QP; e += NT) Ws[e] = 0.f;
       __syncthreads();
       if (bc == 0 && q0 == 0) RC_PHASE(c.ws, c.wo.total, bx, 64);
       if (bc == 0)
-        for (int qq = tid; qq < QT && q0 + qq < Q; qq += RC_BLOCK) {
+        for (int qq = tid; qq < QT && q0 + qq < Q; qq += NT) {
           // squared group norms of the chunk's 16 units (GC, models/cmlp.py:162-166), pre-update
           float sq = 0.f;
           for (int uu = 0; uu < FAC_UC; ++uu) {
@@ -386,19 +430,50 @@ __device__ __attribute__((always_inline)) void fac_fwd_body(const StepCtx& c, in
           ws[c.wo.gq + ((int64_t)uc * K * p + kj) * Q + q0 + qq] = sq;
         }
       if (bc == 0 && q0 == 0) RC_PHASE(c.ws, c.wo.total, bx, 65);
+      if (mf) break;  // (slab: the one column tile; its products follow)
       const int qn = min(QT, Q - q0);
 #pragma unroll 8
       for (int qq = 0; qq < qn; ++qq) {
         const float wv = Ws[tu * QP + qq];
 #pragma unroll
-        for (int i = 0; i < 8; ++i) acc[i] = fmaf(Xs[(tb + 16 * i) * QP + qq], wv, acc[i]);  // rc_fac_bwd.h recomputes this chain
+        for (int i = 0; i < NI; ++i) acc[i] = fmaf(Xs[(tb + (NT / 16) * i) * QP + qq], wv, acc[i]);  // rc_fac_bwd.h recomputes this chain
       }
     }
-    if (bc == 0) RC_PHASE(c.ws, c.wo.total, bx, 66);
     if (bc == 0 && tb == 0 && u < h) ws[c.wo.w1 + (int64_t)kj * h + u] = w1;
+    if (mf) {
+      const float* wr = Ws + l15 * QP;  // A: unit row l15 of the chunk, k = column
+      for (int bt = fwv; bt < (min(FK_BT, c.B - bc) + 15) / 16; bt += NT / 64) {
+        const float* xr = Xs + (16 * bt + l15) * QP;  // B: window 16 bt + l15
+        const f32x4 z = rc_mfma_chain16<FF_KB, true>(
+            f32x4{0.f, 0.f, 0.f, 0.f}, Q, lg, [&](int kc) { return wr[kc]; }, [&](int kc) { return xr[kc]; });
+        if (bc == 0 && bt == 0) RC_PHASE(c.ws, c.wo.total, bx, 66);
+        const int b = bc + 16 * bt + l15;
+        float ys[4];
 #pragma unroll
-    for (int i = 0; i < 8; ++i) {
-      const int b = bc + tb + 16 * i;
+        for (int reg = 0; reg < 4; ++reg) {
+          const int uu = u0 + 4 * lg + reg;
+          ys[reg] = 0.f;
+          if (uu < h) {
+            const float a = fmaxf(z[reg] + bu4[reg], 0.f);
+            if (b < c.B && !rc_fac_recompute(d)) ws[c.wo.a + ((int64_t)kj * d.Bmax + b) * h + uu] = a;
+            ys[reg] = w14[reg] * a;
+          }
+        }
+        // the vector form's butterfly over the 16 units (u ^ 8, ^ 4, ^ 2, ^ 1): unit = 4 lg + reg, so
+        // the first two levels pair lane groups (lanes ^ 32, ^ 16) and the last two pair registers
+#pragma unroll
+        for (int reg = 0; reg < 4; ++reg) ys[reg] += __shfl_xor(ys[reg], 32, 64);
+#pragma unroll
+        for (int reg = 0; reg < 4; ++reg) ys[reg] += __shfl_xor(ys[reg], 16, 64);
+        const float y = (ys[0] + ys[2]) + (ys[1] + ys[3]);
+        if (lg == 0 && b < c.B) ws[c.wo.y + rc_y_idx(d, uc, kj, b)] = y + b1;
+      }
+      continue;
+    }
+    if (bc == 0) RC_PHASE(c.ws, c.wo.total, bx, 66);
+#pragma unroll
+    for (int i = 0; i < NI; ++i) {
+      const int b = bc + tb + (NT / 16) * i;
       float ys = 0.f;
       if (u < h) {
         const float a = fmaxf(acc[i] + bu, 0.f);
@@ -423,23 +498,27 @@ size_t fac_fwd_floats(const RedcliffDims& d) {
 // split: one (window, channel slice) per embedder workgroup (SB = 1), window-major.  NBT: the fc1
 // accumulator columns (windows per workgroup, SB <= NBT): one instantiation per SB keeps the
 // single fit's kernel (NBT = 1) at its own register count, not the 4-window one's.
-template <int NBT>
-__global__ __launch_bounds__(RC_BLOCK) void k_forward(StepCtx c, int SB, int w_lds, int nemb, int cs, int split) {
+// NT: the workgroup's threads -- RC_BLOCK, or RC_EMB_TEAM_NT when every embedder workgroup runs its
+// window's (at most two) fc1 slices as wave teams; MF: the factor products on the matrix cores.
+template <int NBT, int NT, bool MF>
+__global__ __launch_bounds__(NT) void k_forward(StepCtx c, int SB, int w_lds, int nemb, int cs, int split) {
   extern __shared__ float sm[];
   // every step with an embedder forward re-arms the merged backward's factor-lead counter (the
   // kernel boundary orders this store before k_bwd_merged's polls)
   if (blockIdx.x == 0 && nemb > 0 && threadIdx.x == 0)
     *rc_fac_lead_cnt(c, c.ws + rc_rep(c, blockIdx.y) * c.wss) = 0u;  // published factor leads
   if ((int)blockIdx.x < nemb) {
-    if (split) {
+    if (NT == RC_EMB_TEAM_NT) {
+      emb_fwd_body<NBT, NT>(c, blockIdx.x, 1, w_lds, cs, -1, sm);
+    } else if (split) {
       const RcDiv32 dZs = cs == (int)c.mg[RC_MG_CS] ? RcDiv32(c.fzs, c.mg[RC_MG_ZS]) : RcDiv32((c.d.p + cs - 1) / cs);
       const int Zs = dZs.d, b = dZs.div(blockIdx.x);
-      emb_fwd_body<NBT>(c, b, 1, w_lds, cs, blockIdx.x - b * Zs, sm);
+      emb_fwd_body<NBT, NT>(c, b, 1, w_lds, cs, blockIdx.x - b * Zs, sm);
     } else {
-      emb_fwd_body<NBT>(c, blockIdx.x, SB, w_lds, cs, -1, sm);
+      emb_fwd_body<NBT, NT>(c, blockIdx.x, SB, w_lds, cs, -1, sm);
     }
   } else
-    fac_fwd_body(c, blockIdx.x - nemb, sm);
+    fac_fwd_body<NT, MF>(c, blockIdx.x - nemb, sm);
 }
 
 }  // namespace
@@ -495,8 +574,13 @@ void rc_ctx_magics(StepCtx& c) {
 // One launch of the embedder forward (with_emb) and / or the vector-path factor forward (with_fac).
 int rc_launch_forward(const StepCtx& c, hipStream_t s, bool with_emb, bool with_fac, hipEvent_t stop) {
   const RedcliffDims& d = c.d;
-  int SB = 1, w_lds = 1, nemb = 0, split = 0;
+  int SB = 1, w_lds = 1, nemb = 0, split = 0, team = 0;
   const int cs = rc_emb_fwd_slice_channels(d);
+  // REDCLIFF_FWD_MFMA=0: the factor products of the 512-thread launch as the vector loop;
+  // REDCLIFF_EMB_FWD_TEAMS=0: a window's fc1 slices on workgroups of their own (both read per call:
+  // the same bits either way)
+  const char* fmv = getenv("REDCLIFF_FWD_MFMA");
+  const char* tmv = getenv("REDCLIFF_EMB_FWD_TEAMS");
   size_t lds = 0;
   if (with_emb) {
     static const int sb_env = [] {
@@ -514,9 +598,12 @@ int rc_launch_forward(const StepCtx& c, hipStream_t s, bool with_emb, bool with_
     if (emb_fwd_floats(d, SB, w_lds) > limit) w_lds = 0;
     if (emb_fwd_floats(d, SB, w_lds) > limit) limit = RC_LDS_MAX_FLOATS;  // large p*F: one workgroup per CU
     if (emb_fwd_floats(d, SB, w_lds) > limit) { rc_set_error("embedder forward: LDS budget exceeded"); return REDCLIFF_ELIMIT; }
-    lds = emb_fwd_floats(d, SB, w_lds);
     nemb = (c.B + SB - 1) / SB;
-    if (SB == 1 && cs < d.p) {  // one window per workgroup: its slices on workgroups of their own
+    // one window per workgroup with at most two fc1 slices: the slices as wave teams of one workgroup
+    team = SB == 1 && (d.p + cs - 1) / cs <= 2 && (!tmv || strcmp(tmv, "0") != 0) &&
+           emb_fwd_floats(d, SB, w_lds, true) <= limit;
+    lds = emb_fwd_floats(d, SB, w_lds, team);
+    if (!team && SB == 1 && cs < d.p) {  // one window per workgroup: its slices on workgroups of their own
       split = 1;
       nemb = c.B * ((d.p + cs - 1) / cs);
     }
@@ -532,19 +619,25 @@ int rc_launch_forward(const StepCtx& c, hipStream_t s, bool with_emb, bool with_
   }
   if (nemb + nfac == 0) return 0;
   lds *= sizeof(float);
+  const int nt = team ? RC_EMB_TEAM_NT : RC_BLOCK;
+  // The matrix-core products run where the workgroups have eight waves (one window tile per wave at
+  // B = 128).  The 256-thread launches keep the vector loop: TST's step measured slower with the
+  // chains, and as an instantiation of their own they need 132 registers (3 waves).
+  const int fmf = team && (!fmv || strcmp(fmv, "0") != 0);
   auto launch = [&](auto kern) {
     int e = lds_optin(kern, lds, "k_forward LDS");
     if (e) return e;
     if (stop)
-      hipExtLaunchKernelGGL(kern, dim3(nemb + nfac, c.nrep), dim3(RC_BLOCK), lds, s, nullptr, stop, 0, c, SB, w_lds, nemb,
+      hipExtLaunchKernelGGL(kern, dim3(nemb + nfac, c.nrep), dim3(nt), lds, s, nullptr, stop, 0, c, SB, w_lds, nemb,
                             cs, split);
     else
-      hipLaunchKernelGGL(kern, dim3(nemb + nfac, c.nrep), dim3(RC_BLOCK), lds, s, c, SB, w_lds, nemb, cs, split);
+      hipLaunchKernelGGL(kern, dim3(nemb + nfac, c.nrep), dim3(nt), lds, s, c, SB, w_lds, nemb, cs, split);
     return rc_check(hipGetLastError(), "k_forward");
   };
-  if (SB == 1) return launch(k_forward<1>);
-  if (SB == 2) return launch(k_forward<2>);
-  return launch(k_forward<4>);
+  if (team) return fmf ? launch(k_forward<1, RC_EMB_TEAM_NT, true>) : launch(k_forward<1, RC_EMB_TEAM_NT, false>);
+  if (SB == 1) return launch(k_forward<1, RC_BLOCK, false>);
+  if (SB == 2) return launch(k_forward<2, RC_BLOCK, false>);
+  return launch(k_forward<4, RC_BLOCK, false>);
 }
 
 int rc_launch_fac_fwd(const StepCtx& c, hipStream_t s) { return rc_launch_forward(c, s, false, true); }

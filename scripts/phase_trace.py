@@ -59,12 +59,15 @@ def main():
     if ph[24] > 0 and ph[16] > 0:  # lead 0 of a merged launch: its marks in time order, us after mark 16
         print("fac_bwd lead 0 marks (us after 16; 24 / 25 = before / after the stage-1 publish, 18 = before stage 2): " +
               "  ".join("%d %.2f" % (i, (ph[i] - ph[16]) / 100.0) for i in sorted((17, 24, 25, 18), key=lambda i: ph[i]) if ph[i] > 0))
-    for lo, hi, label in ((0, 16, "emb_fwd WG0 phases"), (16, 24, "fac_bwd WG0 phases"), (32, 48, "emb_bwd WG0 phases"),
+    for lo, hi, label in ((0, 12, "emb_fwd WG0 phases"), (16, 24, "fac_bwd WG0 phases"), (32, 48, "emb_bwd WG0 phases"),
                             (48, 64, "emb_final adjacency WG phases")):
         t = ph[lo:hi]
         idx = [i for i in range(hi - lo) if t[i] > 0]
         if len(idx) > 1:
             print(label + ": " + "  ".join("%d->%d %.2f" % (lo + a, lo + b, (t[b] - t[a]) / 100.0) for a, b in zip(idx, idx[1:])))
+    if ph[12] > 0 and ph[6] > 0 and ph[7] > 0:  # wave-team forward: mark 12 = both teams' fc1 slice sums are in LDS
+        print("emb_fwd WG0 team exchange: fc1 6->12 %.2f  sum, bias and store 12->7 %.2f"
+              % ((ph[12] - ph[6]) / 100.0, (ph[7] - ph[12]) / 100.0))
     if ph[32] > 0:  # the embedder backward's node workgroup 0 marks in slot order, us after mark 32
         print("emb_bwd WG0 marks (us after 32): " +
               "  ".join("%d %.2f" % (i, (ph[i] - ph[32]) / 100.0) for i in range(32, 48) if ph[i] > 0))
@@ -83,6 +86,7 @@ def main():
     if ff:  # factor forward workgroup 0 (rc_forward.hip): staged, group norms stored, products done, outputs stored
         st1 = tr[1][0::2]
         st0 = int(st1[st1 > 0][0])  # (its slot is its blockIdx.x: the embedder workgroups come first)
+        # (matrix-core form: 66 = wave 0's first chain done, 67 = its epilogue done)
         print("fac_fwd WG0 marks (us after its start; 64 staged, 65 norms, 66 products, 67 stores): " +
               "  ".join("%d %.2f" % (i, (ph[i] - st0) / 100.0) for i in ff))
     for k, name in enumerate(names):
