@@ -363,6 +363,27 @@ def check(rc, what=""):
         raise RuntimeError("redcliff HIP call %s failed (%d): %s" % (what, rc, msg))
 
 
+def ptr(t):
+    """A tensor's address for an argument struct; None (a null pointer) stays None."""
+    return None if t is None else t.data_ptr()
+
+
+def replica_list(args, replicas):
+    """Set args.replicas / args.n_replicas to the rows `replicas` (None: left zero, every row).  Returns the
+    int32 array the pointer refers to: the caller keeps it until the native call has returned."""
+    if replicas is None:
+        return None
+    keep = (ctypes.c_int32 * max(len(replicas), 1))(*[int(r) for r in replicas])
+    args.replicas = ctypes.cast(keep, ctypes.c_void_p)
+    args.n_replicas = len(replicas)
+    return keep
+
+
+def stream_or_current(stream):
+    """`stream`, or torch's current stream when it is None, as the native calls take it."""
+    return ctypes.c_void_p(torch.cuda.current_stream().cuda_stream) if stream is None else stream
+
+
 def train_steps(a, rows, sizes, stream, what, bn_step=0, cemb=None):
     """One launch chain over consecutive batches: batch i is `sizes[i]` windows from row `rows[i]`,
     its BatchNorm statistics `bn_step` doubles after batch i-1's.  redcliff_train_steps, or with

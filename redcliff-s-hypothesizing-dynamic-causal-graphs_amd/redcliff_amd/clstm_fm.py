@@ -36,8 +36,9 @@ import torch.nn as nn
 from . import _native as nat
 from . import kernels
 from . import metrics as M
+from . import packs
 from .clstm import cLSTM
-from .cmlp_fm import DAGNessLoss, FMPack, _segments, _upload
+from .cmlp_fm import DAGNessLoss, _segments, _upload
 from .fit_loop import standalone_copy
 
 LDS_MAX_FLOATS = 40960  # RC_LDS_MAX_FLOATS
@@ -50,10 +51,7 @@ HISTORY_KEYS = ("avg_forecasting_loss", "avg_adj_penalty", "avg_dagness_loss", "
 
 def lstm_fm_path():
     """'fused' (default) or 'generic', from REDCLIFF_LSTM_FM_PATH."""
-    v = os.environ.get("REDCLIFF_LSTM_FM_PATH", "") or "fused"
-    if v not in ("fused", "generic"):
-        raise ValueError("REDCLIFF_LSTM_FM_PATH must be 'fused' or 'generic', not %r" % v)
-    return v
+    return packs.route_from_env("REDCLIFF_LSTM_FM_PATH")
 
 
 def lstm_fm_lds_floats(p, h, C):
@@ -87,8 +85,7 @@ def lstm_fm_supported(p, h, C, Bmax=1, T=None, R=1):
 def lstm_fm_run(d, context, tmax, flags, B, tB, row0, N, X, x_pstride, fac, fac_m, fac_v, fac_stride, hyper, sse, pen,
                 G=None, replicas=None, stream=None):
     """redcliff_lstm_fm_run on device tensors (None = a null pointer); returns its code."""
-    def p_(t):
-        return None if t is None else t.data_ptr()
+    p_ = nat.ptr
     a = nat.LstmFMArgs()
     a.d = d
     a.context, a.tmax = int(context), int(tmax)
@@ -96,18 +93,15 @@ def lstm_fm_run(d, context, tmax, flags, B, tB, row0, N, X, x_pstride, fac, fac_
     a.X, a.x_pstride = p_(X), int(x_pstride)
     a.fac, a.fac_m, a.fac_v, a.fac_stride = p_(fac), p_(fac_m), p_(fac_v), int(fac_stride)
     a.hyper, a.sse, a.pen, a.G = p_(hyper), p_(sse), p_(pen), p_(G)
-    keep = None
-    if replicas is not None:
-        keep = (ctypes.c_int32 * max(len(replicas), 1))(*[int(r) for r in replicas])
-        a.replicas = ctypes.cast(keep, ctypes.c_void_p)
-        a.n_replicas = len(replicas)
-    return nat.lib().redcliff_lstm_fm_run(ctypes.byref(a), stream if stream is not None else kernels.current_stream())
+    keep = nat.replica_list(a, replicas)  # a local, so alive until the call has returned
+    return nat.lib().redcliff_lstm_fm_run(ctypes.byref(a), nat.stream_or_current(stream))
 
 
 # --------------------------------------------------------------------------------------------------
-class LstmPack(FMPack):
-    """R same-shape cLSTM_FM models on the fused route: their parameters are views of fac[r], their
-    optimizers' exp_avg / exp_avg_sq of m[r] / v[r].  bind_optimizer / hyper are FMPack's."""
+class LstmPack(packs.AdamPack):
+    """R same-shape cLSTM_FM models on the fused route (packs.AdamPack; the rows `par` are also named `fac`):
+    parameters by kernels.lstm_layout, the replica's hyper-parameters beside Adam are the two loss
+    coefficients, and only the reference's one plain Adam can be bound."""
 
     def __init__(self, models):
         m0 = models[0]
@@ -115,35 +109,27 @@ class LstmPack(FMPack):
         for m in models:
             if (m.num_series, m.gen_hidden) != (self.p, self.h) or m.wavelet_level is not None:
                 raise ValueError("an LstmPack holds models of one shape, without wavelets")
-        self.models = list(models)
-        self.R = len(models)
-        if not 1 <= self.R <= MAX_REPLICAS:
+        if not 1 <= len(models) <= MAX_REPLICAS:
             raise ValueError("an LstmPack holds 1..%d models" % MAX_REPLICAS)
-        self.device = next(m0.parameters()).device
         kernels.require_gpu(next(m0.parameters()), "cLSTM_FM (fused)")
         self.n = kernels.lstm_layout(self.p, self.h)["total"]
-        self.fac = torch.empty(self.R, self.n, device=self.device, dtype=torch.float32)
-        self.m = torch.zeros_like(self.fac)
-        self.v = torch.zeros_like(self.fac)
-        self.opt = [None] * self.R
-        self.hyper_key, self.hyper_dev = None, None
-        self.params, self.ptrs = [], []
-        with torch.no_grad():
-            for r, mod in enumerate(self.models):
-                pairs = kernels.lstm_views(self.fac[r], mod.factors[0], self.p, self.h)
-                torch._foreach_copy_([v for _, v in pairs],
-                                     [prm.detach().to(self.device).reshape(v.shape) for prm, v in pairs])
-                for prm, view in pairs:
-                    prm.data = view
-                self.params.append([prm for prm, _ in pairs])
-                self.ptrs.append([prm.data_ptr() for prm, _ in pairs])
-                mod._lf_slot = (self, r)
+        self.allocate(models, self.n, next(m0.parameters()).device)
+        self.fac = self.par
+        for r, mod in enumerate(self.models):
+            self.adopt_views(r, kernels.lstm_views(self.fac[r], mod.factors[0], self.p, self.h))
+
+    def check_optimizer(self, r, opt):
+        packs.require_plain_adam(opt, self.params[r], "cLSTM_FM", "model_utils.py:853-874")
+
+    def replica_terms(self, r):
+        m = self.models[r]
+        return {"c_forecast": float(m.FORECAST_COEFF), "c_adj": float(m.ADJ_L1_REG_COEFF)}
 
     def run(self, flags, X, x_pstride, T, tmax, context, B, N, row0=0, active=None, G=None):
         """One redcliff_lstm_fm_run over recordings [row0, row0 + N) of X in batches of B for the
         replicas `active` (None: all).  Returns (sse, pen) device tensors [stepped][nsteps][p] (pen
         None without VALUES)."""
-        reps = list(range(self.R)) if active is None else list(active)
+        reps = self.reps(active)
         nsteps = -(-int(N) // int(B))
         sse = torch.empty(len(reps), nsteps, self.p, device=self.device, dtype=torch.float32)
         pen = torch.empty_like(sse) if flags & nat.VALUES else None
@@ -151,9 +137,7 @@ class LstmPack(FMPack):
             return sse, pen
         stepping = bool(flags & nat.STEP_B)
         if stepping:
-            for r in reps:
-                if self.opt[r] is None:
-                    raise RuntimeError("bind_optimizer before a stepping launch")
+            self.require_optimizers(reps)
         t_base = self.opt[reps[0]]["t"] if self.opt[reps[0]] else 0
         d = lstm_fm_dims(self.p, self.h, Bmax=int(B), T=int(T), R=self.R)
         rc = lstm_fm_run(d, context, tmax, flags, B, t_base + 1, row0, N, X, x_pstride, self.fac,
@@ -161,10 +145,7 @@ class LstmPack(FMPack):
                          sse, pen, G, None if active is None else reps)
         nat.check(rc, "lstm_fm_run")
         if stepping:
-            for r in reps:
-                st = self.opt[r]
-                st["t"] += nsteps
-                st["step"].fill_(float(st["t"]))
+            self.advance(reps, nsteps)
         return sse, pen
 
 
@@ -189,7 +170,9 @@ def _reduce(sse, pen, scale, coef):
 
 
 # --------------------------------------------------------------------------------------------------
-class cLSTM_FM(nn.Module):
+class cLSTM_FM(packs.PackSlot, nn.Module):
+    _slot_key, _pack_class, _unpickled = "_lf_slot", LstmPack, ("_lf_data",)
+
     def __init__(self, num_chans, gen_hidden, embed_hidden_sizes, num_in_timesteps, coeff_dict, num_sims=1,
                  wavelet_level=None, save_path=None):
         super().__init__()
@@ -230,20 +213,6 @@ class cLSTM_FM(nn.Module):
         if not lstm_fm_shape_supported(p, h, context, Bmax=Bmax, T=T):
             return False
         return lstm_fm_supported(p, h, context, Bmax=Bmax, T=T) > 0
-
-    def _slot(self):
-        """(pack, row) holding this model's parameters; a pack of its own unless it sits in one."""
-        slot = self.__dict__.get("_lf_slot")
-        if slot is None or not slot[0].bound(slot[1]):
-            LstmPack([self])
-            slot = self.__dict__["_lf_slot"]
-        return slot
-
-    def __getstate__(self):  # pickles (torch.save, deepcopy) carry the module, not its pack
-        st = dict(self.__dict__)
-        st.pop("_lf_slot", None)
-        st.pop("_lf_data", None)
-        return st
 
     @staticmethod
     def _tmax(T, max_input_length):
@@ -479,22 +448,11 @@ def fit_lstm_baselines(models, optimizers, save_dirs, X_trains, X_vals, context,
         m.fused_eligible(context, tm_va, Bmax=max(va[0]["sizes"]), T=Tva) for m in models)
     fits = [_Fit(models[i], optimizers[i], save_dirs[i]) for i in range(R)]
     if fused:
-        if R == 1:
-            pack, r0 = models[0]._slot()
-            rows = [r0]
-        else:
-            pack = LstmPack(models)
-            rows = list(range(R))
-        for i in range(R):
-            pack.bind_optimizer(rows[i], optimizers[i])
+        pack, rows, _ = packs.acquire(models, optimizers, LstmPack)
         p = pack.p
-        if R == 1:  # the pack may hold other rows: index this model's data by its row with a zero stride
-            Xtr, Xva, xps_tr, xps_va = tr[0]["X"], va[0]["X"], 0, 0
-        else:
-            Xtr = torch.stack([t["X"] for t in tr]).contiguous()
-            Xva = torch.stack([v["X"] for v in va]).contiguous()
-            xps_tr, xps_va = Xtr[0].numel(), Xva[0].numel()
-        G = torch.zeros(pack.R, p, p, device=dev, dtype=torch.float32)
+        Xtr, xps_tr = packs.stack_upload([t["X"] for t in tr], dev)
+        Xva, xps_va = packs.stack_upload([v["X"] for v in va], dev)
+        G =torch.zeros(pack.R, p, p, device=dev, dtype=torch.float32)
         seg_tr, seg_va = _segments(tr[0]["sizes"]), _segments(va[0]["sizes"])
         sc_tr = _step_scale(tr[0]["sizes"], tm_tr - context, context, dev)
         sc_va = _step_scale(va[0]["sizes"], tm_va - context, context, dev)

@@ -33,6 +33,7 @@ import torch.nn as nn
 from . import _native as nat
 from . import kernels
 from . import metrics as M
+from . import packs
 from .cmlp import cMLP
 from .fit_loop import standalone_copy
 
@@ -45,10 +46,7 @@ FM_FLAGS_VALUES = nat.LOSS_FORECAST | nat.LOSS_ADJ | nat.VALUES
 
 def fm_path():
     """'fused' (default) or 'generic', from REDCLIFF_FM_PATH."""
-    v = os.environ.get("REDCLIFF_FM_PATH", "") or "fused"
-    if v not in ("fused", "generic"):
-        raise ValueError("REDCLIFF_FM_PATH must be 'fused' or 'generic', not %r" % v)
-    return v
+    return packs.route_from_env("REDCLIFF_FM_PATH")
 
 
 def fm_lds_floats(p, L, h):
@@ -81,20 +79,15 @@ def fm_supported(p, L, h, Bmax=1, T=None, R=1, K=1):
 def fm_run(d, flags, B, tB, row0, N, X, x_pstride, fac, fac_m, fac_v, fac_stride, hyper, sse, pen, G=None, G0=None,
            replicas=None, stream=None):
     """redcliff_fm_run on device tensors (None = a null pointer); returns its code."""
-    def p_(t):
-        return None if t is None else t.data_ptr()
+    p_ = nat.ptr
     a = nat.FMArgs()
     a.d = d
     a.flags, a.B, a.tB, a.row0, a.N = int(flags), int(B), int(tB), int(row0), int(N)
     a.X, a.x_pstride = p_(X), int(x_pstride)
     a.fac, a.fac_m, a.fac_v, a.fac_stride = p_(fac), p_(fac_m), p_(fac_v), int(fac_stride)
     a.hyper, a.sse, a.pen, a.G, a.G0 = p_(hyper), p_(sse), p_(pen), p_(G), p_(G0)
-    keep = None
-    if replicas is not None:
-        keep = (ctypes.c_int32 * max(len(replicas), 1))(*[int(r) for r in replicas])
-        a.replicas = ctypes.cast(keep, ctypes.c_void_p)
-        a.n_replicas = len(replicas)
-    return nat.lib().redcliff_fm_run(ctypes.byref(a), stream if stream is not None else kernels.current_stream())
+    keep = nat.replica_list(a, replicas)  # a local, so alive until the call has returned
+    return nat.lib().redcliff_fm_run(ctypes.byref(a), nat.stream_or_current(stream))
 
 
 class DAGNessLoss(nn.Module):
@@ -108,9 +101,10 @@ class DAGNessLoss(nn.Module):
 
 
 # --------------------------------------------------------------------------------------------------
-class FMPack:
-    """R same-shape cMLP_FM models on the fused route: their parameters are views of fac[r], their
-    optimizers' exp_avg / exp_avg_sq of m[r] / v[r] (as PackedEngine.bind / bind_optimizer)."""
+class FMPack(packs.AdamPack):
+    """R same-shape cMLP_FM models on the fused route (packs.AdamPack; the rows `par` are also named `fac`):
+    parameters by kernels.factor_layout at K = 1, the replica's hyper-parameters beside Adam are the two
+    loss coefficients, and only the reference's one plain Adam can be bound."""
 
     def __init__(self, models):
         m0 = models[0]
@@ -118,101 +112,27 @@ class FMPack:
         for m in models:
             if (m.num_series, m.gen_lag, list(m.gen_hidden)) != (self.p, self.L, [self.h]):
                 raise ValueError("an FMPack holds models of one shape")
-        self.models = list(models)
-        self.R = len(models)
-        if not fm_supported(self.p, self.L, self.h, R=self.R):
+        if not fm_supported(self.p, self.L, self.h, R=len(models)):
             nat.check(-2, "fm_supported")
-        self.device = next(m0.parameters()).device
         kernels.require_gpu(next(m0.parameters()), "cMLP_FM (fused)")
         self.n = kernels.factor_layout(1, self.p, self.h, self.L)["total"]
-        self.fac = torch.empty(self.R, self.n, device=self.device, dtype=torch.float32)
-        self.m = torch.zeros_like(self.fac)
-        self.v = torch.zeros_like(self.fac)
-        self.opt = [None] * self.R
-        self.hyper_key, self.hyper_dev = None, None
-        self.params, self.ptrs = [], []
-        with torch.no_grad():
-            for r, mod in enumerate(self.models):
-                pairs = kernels.factor_views(self.fac[r], list(mod.factors), self.p, self.h, self.L)
-                torch._foreach_copy_([v for _, v in pairs],
-                                     [prm.detach().to(self.device).reshape(v.shape) for prm, v in pairs])
-                for prm, view in pairs:
-                    prm.data = view
-                self.params.append([prm for prm, _ in pairs])
-                self.ptrs.append([prm.data_ptr() for prm, _ in pairs])
-                mod._fm_slot = (self, r)
+        self.allocate(models, self.n, next(m0.parameters()).device)
+        self.fac = self.par
+        for r, mod in enumerate(self.models):
+            self.adopt_views(r, kernels.factor_views(self.fac[r], list(mod.factors), self.p, self.h, self.L))
 
-    def bound(self, r):
-        """Model r's parameters still point where the pack put them."""
-        return [prm.data_ptr() for prm in self.params[r]] == self.ptrs[r]
+    def check_optimizer(self, r, opt):
+        packs.require_plain_adam(opt, self.params[r], "cMLP_FM", "model_utils.py:789-809")
 
-    def bind_optimizer(self, r, opt):
-        st = self.opt[r]
-        if st is not None and st["opt"] is opt:
-            tv = int(float(st["step"]))  # stepped by torch in between (the generic route)
-            st["t"] = tv
-            return st
-        if not isinstance(opt, torch.optim.Adam):
-            raise NotImplementedError("the fused cMLP_FM step implements torch.optim.Adam (model_utils.py:789-809)")
-        if len(opt.param_groups) != 1:
-            raise NotImplementedError("one parameter group per optimizer expected")
-        grp = opt.param_groups[0]
-        if grp.get("amsgrad") or grp.get("maximize") or grp.get("decoupled_weight_decay", False):
-            raise NotImplementedError("amsgrad / maximize / decoupled weight decay are not used by cMLP_FM")
-        if set(id(x) for x in grp["params"]) != set(id(x) for x in self.params[r]):
-            raise ValueError("the optimizer must own exactly model.gen_model.parameters()")
-        step = 0
-        base = self.fac[r]
-        with torch.no_grad():
-            self.m[r].zero_()
-            self.v[r].zero_()
-            for prm in self.params[r]:
-                s = opt.state.get(prm)
-                off = (prm.data_ptr() - base.data_ptr()) // 4
-                if s and "exp_avg" in s:  # resume from a torch-stepped (or another pack's) optimizer
-                    self.m[r, off:off + prm.numel()] = s["exp_avg"].reshape(-1)
-                    self.v[r, off:off + prm.numel()] = s["exp_avg_sq"].reshape(-1)
-                    step = int(float(s["step"]))
-        st = {"opt": opt, "t": step, "step": torch.tensor(float(step), dtype=torch.float32)}
-        for prm in self.params[r]:
-            off = (prm.data_ptr() - base.data_ptr()) // 4
-            opt.state[prm] = {"step": st["step"], "exp_avg": self.m[r, off:off + prm.numel()].view_as(prm),
-                              "exp_avg_sq": self.v[r, off:off + prm.numel()].view_as(prm)}
-        self.opt[r] = st
-        return st
-
-    def _adam(self, r):
-        st = self.opt[r]
-        if st is None:
-            return (0.0, (0.9, 0.999), 1e-8, 0.0)
-        g = st["opt"].param_groups[0]
-        return (float(g["lr"]), tuple(float(b) for b in g["betas"]), float(g["eps"]), float(g["weight_decay"]))
-
-    def hyper(self, t_base, reps):
-        """Device RedcliffReplicaHyper[R]; the Adam step number of a replica r in `reps` is the
-        launch's tB + t[r] - t_base."""
-        key = tuple((float(m.FORECAST_COEFF), float(m.ADJ_L1_REG_COEFF), self._adam(r),
-                     (self.opt[r]["t"] - t_base) if (self.opt[r] and r in reps) else 0)
-                    for r, m in enumerate(self.models))
-        if key != self.hyper_key:
-            raw = b""
-            for cf, ca, adam, toff in key:
-                h = nat.ReplicaHyper()
-                h.c_forecast, h.c_adj = cf, ca
-                h.bn_eps, h.bn_momentum = 1e-5, 0.1  # unused
-                h.A = nat.adam_hyper(0.0, (0.9, 0.999), 1e-8, 0.0)
-                h.B = nat.adam_hyper(*adam)
-                h.B.t_offset = int(toff)
-                raw += bytes(h)
-            self.hyper_dev = torch.from_numpy(np.frombuffer(raw, dtype=np.uint8).copy()).to(self.device)
-            self.hyper_key = key
-        return self.hyper_dev
+    def replica_terms(self, r):
+        m = self.models[r]
+        return {"c_forecast": float(m.FORECAST_COEFF), "c_adj": float(m.ADJ_L1_REG_COEFF)}
 
     def run(self, flags, X, x_pstride, T, B, N, row0=0, active=None, G=None, G0=None):
         """One redcliff_fm_run over windows [row0, row0 + N) of X in batches of B for the replicas
         `active` (None: all).  Returns (sse, pen) device tensors [stepped][nsteps][p] (pen None
         without VALUES)."""
-        reps = list(range(self.R)) if active is None else list(active)
+        reps = self.reps(active)
         nsteps = -(-int(N) // int(B))
         sse = torch.empty(len(reps), nsteps, self.p, device=self.device, dtype=torch.float32)
         pen = torch.empty_like(sse) if flags & nat.VALUES else None
@@ -220,19 +140,14 @@ class FMPack:
             return sse, pen
         stepping = bool(flags & nat.STEP_B)
         if stepping:
-            for r in reps:
-                if self.opt[r] is None:
-                    raise RuntimeError("bind_optimizer before a stepping launch")
+            self.require_optimizers(reps)
         t_base = self.opt[reps[0]]["t"] if self.opt[reps[0]] else 0
         d = fm_dims(self.p, self.L, self.h, Bmax=int(B), T=int(T), R=self.R)
         rc = fm_run(d, flags, B, t_base + 1, row0, N, X, x_pstride, self.fac, self.m, self.v, self.n,
                     self.hyper(t_base, reps), sse, pen, G, G0, None if active is None else reps)
         nat.check(rc, "fm_run")
         if stepping:
-            for r in reps:
-                st = self.opt[r]
-                st["t"] += nsteps
-                st["step"].fill_(float(st["t"]))
+            self.advance(reps, nsteps)
         return sse, pen
 
 
@@ -281,7 +196,9 @@ def _val_terms(model, sse, pen, sizes, normalized):
 
 
 # --------------------------------------------------------------------------------------------------
-class cMLP_FM(nn.Module):
+class cMLP_FM(packs.PackSlot, nn.Module):
+    _slot_key, _pack_class, _unpickled = "_fm_slot", FMPack, ("_fm_data",)
+
     def __init__(self, num_chans, gen_lag, gen_hidden, embed_hidden_sizes, num_in_timesteps, num_out_timesteps,
                  coeff_dict, num_sims=1, wavelet_level=None, save_path=None):
         super().__init__()
@@ -330,20 +247,6 @@ class cMLP_FM(nn.Module):
         if not fm_shape_supported(p, L, h, Bmax=Bmax, T=T):
             return False
         return fm_supported(p, L, h, Bmax=Bmax, T=T) > 0
-
-    def _slot(self):
-        """(pack, row) holding this model's parameters; a pack of its own unless it sits in one."""
-        slot = self.__dict__.get("_fm_slot")
-        if slot is None or not slot[0].bound(slot[1]):
-            FMPack([self])
-            slot = self.__dict__["_fm_slot"]
-        return slot
-
-    def __getstate__(self):  # pickles (torch.save, deepcopy) carry the module, not its pack
-        st = dict(self.__dict__)
-        st.pop("_fm_slot", None)
-        st.pop("_fm_data", None)
-        return st
 
     # ------------------------------------------------------------------ reference API
     def forward(self, X):
@@ -574,22 +477,11 @@ def fit_baselines(models, optimizers, save_dirs, X_trains, X_vals, GCs, input_le
     fits = [_Fit(models[i], optimizers[i], save_dirs[i], GCs[i]) for i in range(R)]
     gcs_cache = {}
     if fused:
-        if R == 1:
-            pack, r0 = models[0]._slot()
-            rows = [r0]
-        else:
-            pack = FMPack(models)
-            rows = list(range(R))
-        for i in range(R):
-            pack.bind_optimizer(rows[i], optimizers[i])
+        pack, rows, _ = packs.acquire(models, optimizers, FMPack)
         p, L = pack.p, pack.L
-        if R == 1:  # the pack may hold other rows: index this model's data by its row with a zero stride
-            Xtr, Xva, xps_tr, xps_va = tr[0]["X"], va[0]["X"], 0, 0
-        else:
-            Xtr = torch.stack([t["X"] for t in tr]).contiguous()
-            Xva = torch.stack([v["X"] for v in va]).contiguous()
-            xps_tr, xps_va = Xtr[0].numel(), Xva[0].numel()
-        G = torch.zeros(pack.R, p, p, L, device=dev, dtype=torch.float32)
+        Xtr, xps_tr = packs.stack_upload([t["X"] for t in tr], dev)
+        Xva, xps_va = packs.stack_upload([v["X"] for v in va], dev)
+        G =torch.zeros(pack.R, p, p, L, device=dev, dtype=torch.float32)
         G0 = torch.zeros(pack.R, p, p, device=dev, dtype=torch.float32)
         seg_tr, seg_va = _segments(tr[0]["sizes"]), _segments(va[0]["sizes"])
 

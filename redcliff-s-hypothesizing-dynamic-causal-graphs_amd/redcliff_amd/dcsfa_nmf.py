@@ -35,6 +35,7 @@ import torch.nn.functional as F
 from torch.utils.data import DataLoader, TensorDataset, WeightedRandomSampler
 
 from . import _native as nat
+from . import packs
 
 try:
     from sklearn.decomposition import NMF
@@ -57,10 +58,7 @@ ONE_CLASS_MSG = "Only one class present in y_true. ROC AUC score is not defined 
 
 def dcsfa_path():
     """'fused' or 'generic', from REDCLIFF_DCSFA_PATH (read per call)."""
-    v = os.environ.get(ENV, "") or DEFAULT_PATH
-    if v not in ("fused", "generic"):
-        raise ValueError("%s must be 'fused' or 'generic', not %r" % (ENV, v))
-    return v
+    return packs.route_from_env(ENV, DEFAULT_PATH)
 
 
 def unflatten_directed_spectrum_features(x_flat):
@@ -171,16 +169,9 @@ class DcsfaFitPack:
         self.rv = torch.empty_like(self.rm)
         self.ws = torch.empty(self.R * dcsfa_ws_floats(self.H, self.K, DC_BMAX), device=self.device, dtype=torch.float32)
         self.t = 0
-        with torch.no_grad():
-            for r, mod in enumerate(self.models):
-                for prm, (_, off, shp) in zip(mod.packed_parameters(), self.layout):
-                    view = self.par[r, off:off + prm.numel()].view(shp)
-                    view.copy_(prm.detach().to(self.device, torch.float32).reshape(shp))
-                    prm.data = view
-                bn = mod.encoder[1]
-                self.rm[r].copy_(bn.running_mean)
-                self.rv[r].copy_(bn.running_var)
-                bn.running_mean, bn.running_var = self.rm[r], self.rv[r]
+        for r, mod in enumerate(self.models):
+            packs.pack_by_layout(self.par[r], mod.packed_parameters(), self.layout)
+            packs.adopt_bn_stats(mod.encoder[1], self.rm[r], self.rv[r])
 
     def reset_optimizer(self):
         """A fresh AdamW: zero moments, step 0."""
@@ -219,7 +210,7 @@ class DcsfaFitPack:
         loss = torch.empty(self.R, nsteps, 2, device=self.device, dtype=torch.float32)
         a = self._args(mode, B, data, lr)
         a.n, a.idx, a.idx_pstride, a.loss = n, idx.data_ptr(), n, loss.data_ptr()
-        rc = nat.lib().redcliff_dcsfa_run(ctypes.byref(a), ctypes.c_void_p(torch.cuda.current_stream().cuda_stream))
+        rc = nat.lib().redcliff_dcsfa_run(ctypes.byref(a), nat.stream_or_current(None))
         nat.check(rc, "dcsfa_run")
         self.t += nsteps
         for mod in self.models:
@@ -234,7 +225,7 @@ class DcsfaFitPack:
         ev = torch.empty(self.R, nb, 1 + 4 * self.ns, device=self.device, dtype=torch.float64)
         a = self._args(EVAL, DC_BMAX, data, 0.0)
         a.n, a.row0, a.ev = N, 0, ev.data_ptr()
-        rc = nat.lib().redcliff_dcsfa_run(ctypes.byref(a), ctypes.c_void_p(torch.cuda.current_stream().cuda_stream))
+        rc = nat.lib().redcliff_dcsfa_run(ctypes.byref(a), nat.stream_or_current(None))
         nat.check(rc, "dcsfa_run")
         tot = ev.sum(1)
         return tot[:, 0], tot[:, 1:].reshape(self.R, self.ns, 4)

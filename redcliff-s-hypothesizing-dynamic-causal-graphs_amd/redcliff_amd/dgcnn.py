@@ -32,6 +32,7 @@ import torch.nn as nn
 import torch.nn.functional as F_
 
 from . import _native as nat
+from . import packs
 
 M1 = 64  # torcheeg DGCNN fc1 width
 
@@ -116,10 +117,7 @@ class DGCNN(nn.Module):
 # --------------------------------------------------------------------------------------------------
 def dgcnn_path():
     """'fused' (default) or 'generic', from REDCLIFF_DGCNN_PATH."""
-    v = os.environ.get("REDCLIFF_DGCNN_PATH", "") or "fused"
-    if v not in ("fused", "generic"):
-        raise ValueError("REDCLIFF_DGCNN_PATH must be 'fused' or 'generic', not %r" % v)
-    return v
+    return packs.route_from_env("REDCLIFF_DGCNN_PATH")
 
 
 def select_labels(Y, num_features):
@@ -181,8 +179,7 @@ def dgcnn_fit_layout(n, F, layers, H, C):
 def dgcnn_fit_run(d, mode, B, tB, row0, n, nX, X, x_pstride, Y, y_pstride, par, par_m, par_v, par_stride, bn_rm, bn_rv,
                   hyper, loss, pred, ws, replicas=None, stream=None, launches=0):
     """redcliff_dgcnn_fit_run on device tensors (None = a null pointer); returns its code."""
-    def p_(t):
-        return None if t is None else t.data_ptr()
+    p_ = nat.ptr
     a = nat.DgcnnFitArgs()
     a.d = d
     a.launches = int(launches)  # profiling: a mask of the step's three launches (0 = all)
@@ -191,21 +188,15 @@ def dgcnn_fit_run(d, mode, B, tB, row0, n, nX, X, x_pstride, Y, y_pstride, par, 
     a.par, a.par_m, a.par_v, a.par_stride = p_(par), p_(par_m), p_(par_v), int(par_stride)
     a.bn_rm, a.bn_rv, a.hyper, a.loss, a.pred = p_(bn_rm), p_(bn_rv), p_(hyper), p_(loss), p_(pred)
     a.ws, a.ws_bytes = p_(ws), 0 if ws is None else ws.numel() * 4
-    keep = None
-    if replicas is not None:
-        keep = (ctypes.c_int32 * max(len(replicas), 1))(*[int(r) for r in replicas])
-        a.replicas = ctypes.cast(keep, ctypes.c_void_p)
-        a.n_replicas = len(replicas)
-    if stream is None:
-        stream = ctypes.c_void_p(torch.cuda.current_stream().cuda_stream)
-    return nat.lib().redcliff_dgcnn_fit_run(ctypes.byref(a), stream)
+    keep = nat.replica_list(a, replicas)  # a local, so alive until the call has returned
+    return nat.lib().redcliff_dgcnn_fit_run(ctypes.byref(a), nat.stream_or_current(stream))
 
 
 # --------------------------------------------------------------------------------------------------
-class DgcnnFitPack:
-    """R same-shape DGCNN_Model baselines on the fused route: their parameters are views of par[r], their
-    optimizers' exp_avg / exp_avg_sq of m[r] / v[r], their BatchNorm running statistics of rm[r] / rv[r]
-    (as navar.NavarPack)."""
+class DgcnnFitPack(packs.AdamPack):
+    """R same-shape DGCNN_Model baselines on the fused route (packs.AdamPack): parameters by dgcnn_fit_layout,
+    and beside them the BatchNorm running statistics as views of rm[r] / rv[r] (`bound` watches these too);
+    the replica's hyper-parameters beside Adam are BN1's eps and momentum."""
 
     def __init__(self, models):
         m0 = models[0]
@@ -214,102 +205,34 @@ class DgcnnFitPack:
             if m.fit_shape() != self.shape:
                 raise ValueError("a DgcnnFitPack holds models of one shape")
         self.n, self.F, self.layers, self.H, self.C = self.shape
-        self.models = list(models)
-        self.R = len(models)
-        if not dgcnn_fit_supported(*self.shape, R=self.R):
+        if not dgcnn_fit_supported(*self.shape, R=len(models)):
             nat.check(-2, "dgcnn_fit_supported")
-        self.device = m0.dgcnn.A.device
         if not m0.dgcnn.A.is_cuda:
             raise RuntimeError("DGCNN_Model (fused) runs on the MI355X only (HIP kernels); move the model to 'cuda'")
-        self.layout, self.np_ = dgcnn_fit_layout(*self.shape)
-        self.par = torch.empty(self.R, self.np_, device=self.device, dtype=torch.float32)
-        self.m = torch.zeros_like(self.par)
-        self.v = torch.zeros_like(self.par)
+        self.layout, size = dgcnn_fit_layout(*self.shape)
+        self.allocate(models, size, m0.dgcnn.A.device)
         self.rm = torch.empty(self.R, self.F, device=self.device, dtype=torch.float32)
         self.rv = torch.empty_like(self.rm)
-        self.opt = [None] * self.R
-        self.hyper_key, self.hyper_dev = None, None
-        self.ws = None
-        self.params, self.ptrs = [], []
-        with torch.no_grad():
-            for r, mod in enumerate(self.models):
-                prms = mod.packed_parameters()
-                for prm, (_, off, shp) in zip(prms, self.layout):
-                    view = self.par[r, off:off + prm.numel()].view(shp)
-                    view.copy_(prm.detach().to(self.device, torch.float32).reshape(shp))
-                    prm.data = view
-                bn = mod.dgcnn.BN1
-                self.rm[r].copy_(bn.running_mean)
-                self.rv[r].copy_(bn.running_var)
-                bn.running_mean, bn.running_var = self.rm[r], self.rv[r]
-                self.params.append(prms)
-                self.ptrs.append([prm.data_ptr() for prm in prms] + [self.rm[r].data_ptr(), self.rv[r].data_ptr()])
-                mod.__dict__["_dg_slot"] = (self, r)
+        for r, mod in enumerate(self.models):
+            prms = mod.packed_parameters()
+            packs.pack_by_layout(self.par[r], prms, self.layout)
+            packs.adopt_bn_stats(mod.dgcnn.BN1, self.rm[r], self.rv[r])
+            self.adopt(r, prms)
 
-    def bound(self, r):
+    def extra_pointers(self, r):
         bn = self.models[r].dgcnn.BN1
-        return [prm.data_ptr() for prm in self.params[r]] + [bn.running_mean.data_ptr(), bn.running_var.data_ptr()] == \
-            self.ptrs[r]
+        return [bn.running_mean.data_ptr(), bn.running_var.data_ptr()]
 
     def stepped_parameters(self, r):
-        """The parameters Adam holds state for: all of them, but A with one layer (it has no gradient)."""
+        """All of them, but A with one layer (it has no gradient)."""
         return self.params[r][1:] if self.layers == 1 else self.params[r]
 
-    def bind_optimizer(self, r, opt):
-        st = self.opt[r]
-        if st is not None and st["opt"] is opt:
-            st["t"] = int(float(st["step"]))  # stepped by torch in between (the generic route)
-            return st
-        step = 0
-        base = self.par[r]
-        with torch.no_grad():
-            self.m[r].zero_()
-            self.v[r].zero_()
-            for prm in self.stepped_parameters(r):
-                s = opt.state.get(prm)
-                off = (prm.data_ptr() - base.data_ptr()) // 4
-                if s and "exp_avg" in s:  # resume from a torch-stepped (or another pack's) optimizer
-                    self.m[r, off:off + prm.numel()] = s["exp_avg"].reshape(-1)
-                    self.v[r, off:off + prm.numel()] = s["exp_avg_sq"].reshape(-1)
-                    step = int(float(s["step"]))
-        st = {"opt": opt, "t": step, "step": torch.tensor(float(step), dtype=torch.float32)}
-        for prm in self.stepped_parameters(r):
-            off = (prm.data_ptr() - base.data_ptr()) // 4
-            opt.state[prm] = {"step": st["step"], "exp_avg": self.m[r, off:off + prm.numel()].view_as(prm),
-                              "exp_avg_sq": self.v[r, off:off + prm.numel()].view_as(prm)}
-        self.opt[r] = st
-        return st
-
-    def _adam(self, r):
-        st = self.opt[r]
-        if st is None:
-            return (0.0, (0.9, 0.999), 1e-8, 0.0)
-        g = st["opt"].param_groups[0]
-        return (float(g["lr"]), tuple(float(b) for b in g["betas"]), float(g["eps"]), float(g["weight_decay"]))
-
-    def hyper(self, t_base, reps):
-        """Device RedcliffReplicaHyper[R]: bn_eps / bn_momentum of BN1, B = Adam; a replica's Adam step
-        number is the launch's tB + t[r] - t_base."""
-        key = tuple((float(self.models[r].dgcnn.BN1.eps), float(self.models[r].dgcnn.BN1.momentum), self._adam(r),
-                     (self.opt[r]["t"] - t_base) if (self.opt[r] and r in reps) else 0) for r in range(self.R))
-        if key != self.hyper_key:
-            raw = b""
-            for eps, mom, adam, toff in key:
-                h = nat.ReplicaHyper()
-                h.bn_eps, h.bn_momentum = eps, mom
-                h.A = nat.adam_hyper(0.0, (0.9, 0.999), 1e-8, 0.0)
-                h.B = nat.adam_hyper(*adam)
-                h.B.t_offset = int(toff)
-                raw += bytes(h)
-            self.hyper_dev = torch.from_numpy(np.frombuffer(raw, dtype=np.uint8).copy()).to(self.device)
-            self.hyper_key = key
-        return self.hyper_dev
+    def replica_terms(self, r):
+        bn = self.models[r].dgcnn.BN1
+        return {"bn_eps": float(bn.eps), "bn_momentum": float(bn.momentum)}
 
     def workspace(self, B, n, nrep):
-        need = dgcnn_fit_ws_floats(*self.shape, B, n) * max(nrep, 1)
-        if self.ws is None or self.ws.numel() < need:
-            self.ws = torch.empty(need, device=self.device, dtype=torch.float32)
-        return self.ws
+        return self.workspace_of(dgcnn_fit_ws_floats(*self.shape, B, n) * max(nrep, 1))
 
     def dims(self, B, T):
         return dgcnn_fit_dims(*self.shape, Bmax=int(B), T=int(T), R=self.R)
@@ -318,14 +241,12 @@ class DgcnnFitPack:
         """One TRAIN call: ceil(n / B) Adam steps over rows [row0, row0 + n) for the replicas `active`
         (None: all).  X (.., nX, T, nodes), Y (.., nX, C) float32 on the device.  Returns the steps'
         losses, a device tensor [stepped][nsteps]."""
-        reps = list(range(self.R)) if active is None else list(active)
+        reps = self.reps(active)
         nsteps = -(-int(n) // int(B))
         loss = torch.empty(len(reps), nsteps, device=self.device, dtype=torch.float32)
         if not reps or n == 0:
             return loss
-        for r in reps:
-            if self.opt[r] is None:
-                raise RuntimeError("bind_optimizer before a stepping call")
+        self.require_optimizers(reps)
         t_base = self.opt[reps[0]]["t"]
         T, nX = int(X.shape[-2]), int(X.shape[-3])
         ws = self.workspace(B, n, len(reps)) if ws is None else ws
@@ -333,17 +254,15 @@ class DgcnnFitPack:
                            self.v, self.np_, self.rm, self.rv, self.hyper(t_base, reps), loss, None, ws,
                            None if active is None else reps, launches=launches)
         nat.check(rc, "dgcnn_fit_run")
+        self.advance(reps, nsteps)
         for r in reps:
-            st = self.opt[r]
-            st["t"] += nsteps
-            st["step"].fill_(float(st["t"]))
             self.models[r].dgcnn.BN1.num_batches_tracked += nsteps
         return loss
 
     def forward(self, X, x_pstride, Y, y_pstride, row0, n, B, active=None, ws=None):
         """One FORWARD call (eval mode) over rows [row0, row0 + n) in batches of B: (pred [stepped][n][C],
         per-batch MSE [stepped][nbatches] or None without labels)."""
-        reps = list(range(self.R)) if active is None else list(active)
+        reps = self.reps(active)
         nb = -(-int(n) // int(B))
         pred = torch.empty(len(reps), n, self.C, device=self.device, dtype=torch.float32)
         mse = None if Y is None else torch.empty(len(reps), nb, device=self.device, dtype=torch.float32)
@@ -358,10 +277,11 @@ class DgcnnFitPack:
 
 
 # --------------------------------------------------------------------------------------------------
-class DGCNN_Model(nn.Module):
+class DGCNN_Model(packs.PackSlot, nn.Module):
     """models/dgcnn.py:15-237: the DGCNN wrapper REDCLIFF-S embeds, and the supervised baseline with the
     reference's forward / batch_update / training_eval / save_checkpoint / fit (see the module docstring
     for the fit's two routes)."""
+    _slot_key, _pack_class = "_dg_slot", DgcnnFitPack
 
     def __init__(self, num_channels, num_wavelets_per_chan, num_features_per_node, num_graph_conv_layers,
                  num_hidden_nodes, num_classes):
@@ -450,18 +370,13 @@ class DGCNN_Model(nn.Module):
         if dgcnn_path() != "fused":
             return False
         bn = self.dgcnn.BN1
-        if not (type(self.supervised_loss_fn) is nn.MSELoss and self.supervised_loss_fn.reduction == "mean"):
+        if not packs.mean_mse(self.supervised_loss_fn):
             return False
         if not (bn.affine and bn.track_running_stats and bn.momentum is not None):
             return False
         if optimizer is not None:
-            if type(optimizer) is not torch.optim.Adam or len(optimizer.param_groups) != 1:
-                return False
-            g = optimizer.param_groups[0]
-            if g.get("amsgrad") or g.get("maximize") or g.get("decoupled_weight_decay", False):
-                return False
-            if set(id(p) for p in g["params"]) != set(id(p) for p in self.dgcnn.parameters()) or \
-                    len(g["params"]) != len(list(self.dgcnn.parameters())):
+            mine = list(self.dgcnn.parameters())
+            if not packs.plain_adam(optimizer, mine) or len(optimizer.param_groups[0]["params"]) != len(mine):
                 return False
         tensors = list(self.parameters()) + [bn.running_mean, bn.running_var]
         if not all(p.is_cuda and p.dtype == torch.float32 for p in tensors):
@@ -470,19 +385,6 @@ class DGCNN_Model(nn.Module):
         if not dgcnn_fit_lds_floats(*args):
             return False
         return dgcnn_fit_supported(*args) > 0
-
-    def _slot(self):
-        """(pack, row) holding this model's parameters; a pack of its own unless it sits in one."""
-        slot = self.__dict__.get("_dg_slot")
-        if slot is None or not slot[0].bound(slot[1]):
-            DgcnnFitPack([self])
-            slot = self.__dict__["_dg_slot"]
-        return slot
-
-    def __getstate__(self):  # pickles (torch.save, deepcopy) carry the module, not its pack
-        st = dict(self.__dict__)
-        st.pop("_dg_slot", None)
-        return st
 
     def fit(self, save_dir, train_loader, gen_optim, max_iter, lookback, check_every, verbose, GC, val_loader):
         return fit_dgcnn_baselines([self], [save_dir], [train_loader], [gen_optim], max_iter, lookback, check_every, verbose,
@@ -602,21 +504,11 @@ def fit_dgcnn_baselines(models, save_dirs, train_loaders, optimizers, max_iter, 
     if not good:
         return one_by_one() if R > 1 else generic()
     # ---------------------------------------------------------------- fused
-    if R == 1:
-        pack, r0 = m0._slot()
-        rows = [r0]
-    else:
-        pack = DgcnnFitPack(models)
-        rows = list(range(R))
+    pack, rows, _ = packs.acquire(models, optimizers, DgcnnFitPack)
     dev = pack.device
-    for i in range(R):
-        pack.bind_optimizer(rows[i], optimizers[i])
 
     def upload(sets, k):
-        if R == 1:  # the pack may hold other rows: a zero stride serves this model's row
-            return sets[0][k].to(dev), 0
-        t = torch.stack([s[k] for s in sets]).to(dev)
-        return t, t[0].numel()
+        return packs.stack_upload([s[k] for s in sets], dev)
     Xtr, xps = upload(tr, 0)
     Ytr, yps = upload(tr, 1)
     Xva, xps_va = upload(va, 0)

@@ -19,6 +19,7 @@ Two routes, chosen by ``REDCLIFF_NAVAR_PATH=fused|generic`` (default fused):
 train/NAVAR_CMLP_d4IC_BCTVgs1Parsim.py) with the replica on a grid axis; ``NAVAR.fit`` is that function
 with lists of one.  NAVARLSTM (models/navar.py:129-246) is redcliff_amd.navar_lstm.
 """
+import collections
 import ctypes
 import os
 
@@ -27,6 +28,7 @@ import torch
 import torch.nn as nn
 
 from . import _native as nat
+from . import packs
 
 LDS_MAX_FLOATS = 40960  # RC_LDS_MAX_FLOATS
 NV_BC, NV_SL, NV_MISC = 64, 32, 240  # csrc/rc_navar.h
@@ -36,10 +38,7 @@ TRAIN, FORWARD = 0, 1
 
 def navar_path():
     """'fused' (default) or 'generic', from REDCLIFF_NAVAR_PATH."""
-    v = os.environ.get("REDCLIFF_NAVAR_PATH", "") or "fused"
-    if v not in ("fused", "generic"):
-        raise ValueError("REDCLIFF_NAVAR_PATH must be 'fused' or 'generic', not %r" % v)
-    return v
+    return packs.route_from_env("REDCLIFF_NAVAR_PATH")
 
 
 def navar_lds_floats(N, H, K, layers=1, Bmax=1, T=None, R=1):
@@ -85,33 +84,35 @@ def navar_layout(N, H, K, layers):
     return out, at
 
 
-def navar_run(d, mode, B, tB, row0, n, nX, X, x_pstride, perm, perm_pstride, par, par_m, par_v, par_stride, hyper,
-              mse, l1, pred, contrib, ws, replicas=None, stream=None, launches=0):
-    """redcliff_navar_run on device tensors (None = a null pointer); returns its code."""
-    def p_(t):
-        return None if t is None else t.data_ptr()
-    a = nat.NavarArgs()
+def _run(Args, entry, d, mode, B, tB, row0, n, nX, X, x_pstride, perm, perm_pstride, par, par_m, par_v, par_stride, hyper,
+         mse, l1, pred, contrib, ws, replicas, stream, launches):
+    """The native call `entry` of the NAVAR family (RedcliffNavarArgs and RedcliffNavarLstmArgs have the
+    same fields) on device tensors (None = a null pointer); returns its code."""
+    p_ = nat.ptr
+    a = Args()
     a.d = d
-    a.launches = int(launches)  # profiling: a mask of the step's three launches (0 = all)
+    a.launches = int(launches)  # profiling: a mask of the step's launches (0 = all)
     a.mode, a.B, a.tB, a.row0, a.N, a.nX = int(mode), int(B), int(tB), int(row0), int(n), int(nX)
     a.X, a.x_pstride, a.perm, a.perm_pstride = p_(X), int(x_pstride), p_(perm), int(perm_pstride)
     a.par, a.par_m, a.par_v, a.par_stride, a.hyper = p_(par), p_(par_m), p_(par_v), int(par_stride), p_(hyper)
     a.mse, a.l1, a.pred, a.contrib = p_(mse), p_(l1), p_(pred), p_(contrib)
     a.ws, a.ws_bytes = p_(ws), 0 if ws is None else ws.numel() * 4
-    keep = None
-    if replicas is not None:
-        keep = (ctypes.c_int32 * max(len(replicas), 1))(*[int(r) for r in replicas])
-        a.replicas = ctypes.cast(keep, ctypes.c_void_p)
-        a.n_replicas = len(replicas)
-    if stream is None:
-        stream = ctypes.c_void_p(torch.cuda.current_stream().cuda_stream)
-    return nat.lib().redcliff_navar_run(ctypes.byref(a), stream)
+    keep = nat.replica_list(a, replicas)  # a local, so alive until the call has returned
+    return getattr(nat.lib(), entry)(ctypes.byref(a), nat.stream_or_current(stream))
+
+
+def navar_run(d, mode, B, tB, row0, n, nX, X, x_pstride, perm, perm_pstride, par, par_m, par_v, par_stride, hyper,
+              mse, l1, pred, contrib, ws, replicas=None, stream=None, launches=0):
+    """redcliff_navar_run on device tensors (None = a null pointer); returns its code.  `launches` masks the
+    step's three launches."""
+    return _run(nat.NavarArgs, "redcliff_navar_run", d, mode, B, tB, row0, n, nX, X, x_pstride, perm, perm_pstride, par,
+                par_m, par_v, par_stride, hyper, mse, l1, pred, contrib, ws, replicas, stream, launches)
 
 
 # --------------------------------------------------------------------------------------------------
-class NavarPack:
-    """R same-shape NAVAR models on the fused route: their parameters are views of par[r], their
-    optimizers' exp_avg / exp_avg_sq of m[r] / v[r] (as cmlp_fm.FMPack)."""
+class NavarPack(packs.AdamPack):
+    """R same-shape NAVAR models on the fused route (packs.AdamPack): parameters by navar_layout, the
+    replica's hyper-parameter beside Adam is c_adj = lambda1."""
 
     def __init__(self, models):
         m0 = models[0]
@@ -119,92 +120,23 @@ class NavarPack:
         for m in models:
             if (m.num_nodes, m.num_hidden, m.maxlags, m.hidden_layers) != (self.N, self.H, self.K, self.layers):
                 raise ValueError("a NavarPack holds models of one shape")
-        self.models = list(models)
-        self.R = len(models)
-        if not navar_supported(self.N, self.H, self.K, self.layers, R=self.R):
+        if not navar_supported(self.N, self.H, self.K, self.layers, R=len(models)):
             nat.check(-2, "navar_supported")
-        self.device = m0.biases.device
         if not m0.biases.is_cuda:
             raise RuntimeError("NAVAR (fused) runs on the MI355X only (HIP kernels); move the model to 'cuda'")
         self.layout, self.n = navar_layout(self.N, self.H, self.K, self.layers)
-        self.par = torch.empty(self.R, self.n, device=self.device, dtype=torch.float32)
-        self.m = torch.zeros_like(self.par)
-        self.v = torch.zeros_like(self.par)
-        self.opt = [None] * self.R
+        self.allocate(models, self.n, m0.biases.device)
         self.lambda1 = [0.0] * self.R
-        self.hyper_key, self.hyper_dev = None, None
-        self.ws = None
-        self.params, self.ptrs = [], []
-        with torch.no_grad():
-            for r, mod in enumerate(self.models):
-                prms = mod.packed_parameters()
-                for prm, (_, off, shp) in zip(prms, self.layout):
-                    view = self.par[r, off:off + prm.numel()].view(shp)
-                    view.copy_(prm.detach().to(self.device, torch.float32).reshape(shp))
-                    prm.data = view
-                self.params.append(prms)
-                self.ptrs.append([prm.data_ptr() for prm in prms])
-                mod.__dict__["_nv_slot"] = (self, r)
+        for r, mod in enumerate(self.models):
+            prms = mod.packed_parameters()
+            packs.pack_by_layout(self.par[r], prms, self.layout)
+            self.adopt(r, prms)
 
-    def bound(self, r):
-        return [prm.data_ptr() for prm in self.params[r]] == self.ptrs[r]
-
-    def bind_optimizer(self, r, opt):
-        st = self.opt[r]
-        if st is not None and st["opt"] is opt:
-            st["t"] = int(float(st["step"]))  # stepped by torch in between (the generic route)
-            return st
-        step = 0
-        base = self.par[r]
-        with torch.no_grad():
-            self.m[r].zero_()
-            self.v[r].zero_()
-            for prm in self.params[r]:
-                s = opt.state.get(prm)
-                off = (prm.data_ptr() - base.data_ptr()) // 4
-                if s and "exp_avg" in s:  # resume from a torch-stepped (or another pack's) optimizer
-                    self.m[r, off:off + prm.numel()] = s["exp_avg"].reshape(-1)
-                    self.v[r, off:off + prm.numel()] = s["exp_avg_sq"].reshape(-1)
-                    step = int(float(s["step"]))
-        st = {"opt": opt, "t": step, "step": torch.tensor(float(step), dtype=torch.float32)}
-        for prm in self.params[r]:
-            off = (prm.data_ptr() - base.data_ptr()) // 4
-            opt.state[prm] = {"step": st["step"], "exp_avg": self.m[r, off:off + prm.numel()].view_as(prm),
-                              "exp_avg_sq": self.v[r, off:off + prm.numel()].view_as(prm)}
-        self.opt[r] = st
-        return st
-
-    def _adam(self, r):
-        st = self.opt[r]
-        if st is None:
-            return (0.0, (0.9, 0.999), 1e-8, 0.0)
-        g = st["opt"].param_groups[0]
-        return (float(g["lr"]), tuple(float(b) for b in g["betas"]), float(g["eps"]), float(g["weight_decay"]))
-
-    def hyper(self, t_base, reps):
-        """Device RedcliffReplicaHyper[R]: c_adj = lambda1, B = Adam; a replica's Adam step number is
-        the launch's tB + t[r] - t_base."""
-        key = tuple((float(self.lambda1[r]), self._adam(r), (self.opt[r]["t"] - t_base) if (self.opt[r] and r in reps) else 0)
-                    for r in range(self.R))
-        if key != self.hyper_key:
-            raw = b""
-            for lam, adam, toff in key:
-                h = nat.ReplicaHyper()
-                h.c_adj = lam
-                h.bn_eps, h.bn_momentum = 1e-5, 0.1  # unused
-                h.A = nat.adam_hyper(0.0, (0.9, 0.999), 1e-8, 0.0)
-                h.B = nat.adam_hyper(*adam)
-                h.B.t_offset = int(toff)
-                raw += bytes(h)
-            self.hyper_dev = torch.from_numpy(np.frombuffer(raw, dtype=np.uint8).copy()).to(self.device)
-            self.hyper_key = key
-        return self.hyper_dev
+    def replica_terms(self, r):
+        return {"c_adj": float(self.lambda1[r])}
 
     def workspace(self, B, nrep):
-        need = navar_ws_floats(self.N, self.H, self.layers, B) * max(nrep, 1)
-        if self.ws is None or self.ws.numel() < need:
-            self.ws = torch.empty(need, device=self.device, dtype=torch.float32)
-        return self.ws
+        return self.workspace_of(navar_ws_floats(self.N, self.H, self.layers, B) * max(nrep, 1))
 
     def dims(self, B, T):
         return navar_dims(self.N, self.H, self.K, self.layers, Bmax=int(B), T=int(T), R=self.R)
@@ -213,15 +145,13 @@ class NavarPack:
         """One TRAIN call: ceil(n / B) Adam steps over perm[0 .. n) for the replicas `active` (None:
         all).  X (.., nX, T, N) float32, perm int32 on the device.  Returns (mse, l1) device tensors
         [stepped][nsteps]."""
-        reps = list(range(self.R)) if active is None else list(active)
+        reps = self.reps(active)
         nsteps = -(-int(n) // int(B))
         mse = torch.empty(len(reps), nsteps, device=self.device, dtype=torch.float32)
         l1 = torch.empty_like(mse)
         if not reps or n == 0:
             return mse, l1
-        for r in reps:
-            if self.opt[r] is None:
-                raise RuntimeError("bind_optimizer before a stepping call")
+        self.require_optimizers(reps)
         t_base = self.opt[reps[0]]["t"]
         T, nX = int(X.shape[-2]), int(X.shape[-3])
         ws = self.workspace(B, len(reps)) if ws is None else ws
@@ -229,15 +159,12 @@ class NavarPack:
                        self.m, self.v, self.n, self.hyper(t_base, reps), mse, l1, None, None, ws,
                        None if active is None else reps)
         nat.check(rc, "navar_run")
-        for r in reps:
-            st = self.opt[r]
-            st["t"] += nsteps
-            st["step"].fill_(float(st["t"]))
+        self.advance(reps, nsteps)
         return mse, l1
 
     def forward(self, X, x_pstride, row0, n, active=None, B=None, ws=None):
         """One FORWARD call over rows [row0, row0 + n): (pred [stepped][n][N], contrib [stepped][n][N*N])."""
-        reps = list(range(self.R)) if active is None else list(active)
+        reps = self.reps(active)
         pred = torch.empty(len(reps), n, self.N, device=self.device, dtype=torch.float32)
         contrib = torch.empty(len(reps), n, self.N * self.N, device=self.device, dtype=torch.float32)
         if not reps or n == 0:
@@ -252,7 +179,17 @@ class NavarPack:
 
 
 # --------------------------------------------------------------------------------------------------
-class NAVAR(nn.Module):
+def _plain_fit(model, criterion, optimizer):
+    """The loss and the optimizer (when given) are the ones the family's fused steps implement: mean MSE,
+    and packs.plain_adam over the model's parameters."""
+    if criterion is not None and not packs.mean_mse(criterion):
+        return False
+    return optimizer is None or packs.plain_adam(optimizer, list(model.parameters()))
+
+
+class NAVAR(packs.PackSlot, nn.Module):
+    _slot_key, _pack_class = "_nv_slot", NavarPack
+
     def __init__(self, num_nodes, num_hidden, maxlags, hidden_layers=1, dropout=0):
         super().__init__()
         self.num_nodes = num_nodes
@@ -303,35 +240,14 @@ class NAVAR(nn.Module):
             return False
         if T is not None and T - 1 != self.maxlags:
             return False
-        if criterion is not None and not (type(criterion) is nn.MSELoss and criterion.reduction == "mean"):
+        if not _plain_fit(self, criterion, optimizer):
             return False
-        if optimizer is not None:
-            if type(optimizer) is not torch.optim.Adam or len(optimizer.param_groups) != 1:
-                return False
-            g = optimizer.param_groups[0]
-            if g.get("amsgrad") or g.get("maximize") or g.get("decoupled_weight_decay", False):
-                return False
-            if set(id(p) for p in g["params"]) != set(id(p) for p in self.parameters()):
-                return False
         if not all(p.is_cuda and p.dtype == torch.float32 for p in self.parameters()):
             return False
         args = (self.num_nodes, self.num_hidden, self.maxlags, self.hidden_layers, int(Bmax), T)
         if not navar_lds_floats(*args):
             return False
         return navar_supported(*args) > 0
-
-    def _slot(self):
-        """(pack, row) holding this model's parameters; a pack of its own unless it sits in one."""
-        slot = self.__dict__.get("_nv_slot")
-        if slot is None or not slot[0].bound(slot[1]):
-            NavarPack([self])
-            slot = self.__dict__["_nv_slot"]
-        return slot
-
-    def __getstate__(self):  # pickles (torch.save, deepcopy) carry the module, not its pack
-        st = dict(self.__dict__)
-        st.pop("_nv_slot", None)
-        return st
 
     def fit(self, save_path, X_train, Y_train, criterion, optimizer, X_val=None, Y_val=None, val_proportion=0.0,
             epochs=200, batch_size=300, split_timeseries=False, check_every=1000, lambda1=0, rng=None):
@@ -363,15 +279,27 @@ def _save(model, save_path):
     torch.save(_standalone(model), os.path.join(save_path, "final_best_model.bin"))
 
 
-def _fit_generic(model, save_path, X_train, criterion, optimizer, X_val, val_proportion, epochs, batch_size,
+# What tells the family's two members apart in the shared drivers: the driver's name (for its error text), the
+# pack class, the shape key of models that share a pack, eligible(model, criterion, optimizer, T, Bmax,
+# split_timeseries) with the member's own terms, and `recurrent`: predictions carry a time axis whose last
+# step is the forecast, the data is cast to the model's dtype and a fit starts by model.train() (a fit
+# leaves the model in eval mode, as the reference; the GPU's fused LSTM backward refuses such a module).
+_Family = collections.namedtuple("_Family", "name pack shape eligible recurrent")
+
+
+def _fit_generic(fam, model, save_path, X_train, criterion, optimizer, X_val, val_proportion, epochs, batch_size,
                  split_timeseries, check_every, lambda1, rng, verbose):
-    dev = model.biases.device
-    X_train = torch.from_numpy(np.swapaxes(X_train, 2, 1)).to(dev)
+    """The reference's loop (models/navar.py:57-125 and :181-246) with torch autograd and the caller's optimizer."""
+    dev, dt = model.biases.device, model.biases.dtype if fam.recurrent else None
+    forecast = (lambda pred: pred[:, :, -1]) if fam.recurrent else (lambda pred: pred)
+    X_train = torch.from_numpy(np.swapaxes(X_train, 2, 1)).to(dev, dt)
     if X_val is not None:
-        X_val = torch.from_numpy(np.swapaxes(X_val, 2, 1)).to(dev)
+        X_val = torch.from_numpy(np.swapaxes(X_val, 2, 1)).to(dev, dt)
     n = X_train.size()[0]
     total_loss, loss_val, batch_counter = 0, 0, 0
     history = []
+    if fam.recurrent:
+        model.train()
     for t in range(1, epochs + 1):
         _, batches = _epoch_batches(rng, n, batch_size)
         for idx in batches:
@@ -381,7 +309,7 @@ def _fit_generic(model, save_path, X_train, criterion, optimizer, X_val, val_pro
             X_batch, Y_batch = xb[:, :, :-1], xb[:, :, -1]
             predictions, contributions = model.forward(X_batch)
             if not split_timeseries:
-                loss_pred = criterion(predictions, Y_batch)
+                loss_pred = criterion(forecast(predictions), Y_batch)
             else:
                 loss_pred = criterion(predictions[:, :, -1], Y_batch[:, :, -1])
             loss_l1 = (lambda1 / model.num_nodes) * torch.mean(torch.sum(torch.abs(contributions), dim=1))
@@ -393,10 +321,11 @@ def _fit_generic(model, save_path, X_train, criterion, optimizer, X_val, val_pro
             optimizer.step()
         if t % check_every == 0:
             model.eval()
-            if val_proportion > 0.0:
+            if val_proportion > 0.0 and X_val is not None:
                 with torch.no_grad():
                     val_pred, _ = model.forward(X_val[:, :, :-1])
-                    loss_val = criterion(val_pred, X_val[:, :, -1])
+                    # (NAVARLSTM: the reference's line compares (n, N, T') with (n, N) and cannot broadcast)
+                    loss_val = criterion(forecast(val_pred), X_val[:, :, -1])
             model.train()
             if verbose:
                 print(f'iteration {t}. Loss: {total_loss / batch_counter}  Val loss: {loss_val}')
@@ -411,55 +340,44 @@ def _fit_generic(model, save_path, X_train, criterion, optimizer, X_val, val_pro
     return loss_val
 
 
-def fit_navar_baselines(models, save_paths, X_trains, criterion, optimizers, X_vals=None, val_proportion=0.0, epochs=200,
-                        batch_size=300, check_every=1000, lambda1=0, rngs=None, verbose=0, split_timeseries=False):
-    """NAVAR.fit (models/navar.py:57-125) for a list of models, each with its own data (n, T, N),
-    optimizer, save_path and RNG (None: the global numpy.random module, as the reference).  Same-shape
-    models with equal n on the fused route share one native call per epoch; otherwise one fit after
-    the other.  Returns the fits' loss_val; every model's per-step (mse, l1) values are left in
-    ``model.step_losses``."""
+def _fit_navar_family(fam, models, save_paths, X_trains, criterion, optimizers, X_vals, val_proportion, epochs,
+                      batch_size, check_every, lambda1, rngs, verbose, split_timeseries):
+    """The fit of the reference's NAVAR and NAVARLSTM (models/navar.py:57-125 and :181-246) for a list of
+    models of the member `fam`, each with its own data (n, T, N), optimizer, save_path and RNG (None: the
+    global numpy.random module, as the reference).  Same-shape models with equal n on the fused route share
+    one native call per epoch; otherwise one fit after the other.  Returns the fits' loss_val; every model's
+    per-step (mse, l1) values are left in ``model.step_losses``."""
     R = len(models)
     X_vals = [None] * R if X_vals is None else list(X_vals)
     rngs = [None] * R if rngs is None else list(rngs)
     lams = list(lambda1) if isinstance(lambda1, (list, tuple)) else [lambda1] * R
     if not (len(save_paths) == len(X_trains) == len(optimizers) == len(X_vals) == len(rngs) == len(lams) == R) or R == 0:
-        raise ValueError("fit_navar_baselines: one save_path, training set, optimizer and rng per model")
+        raise ValueError("%s: one save_path, training set, optimizer and rng per model" % fam.name)
     rngs = [np.random if g is None else g for g in rngs]
     m0 = models[0]
-    shape = lambda m: (m.num_nodes, m.num_hidden, m.maxlags, m.hidden_layers)
-    same = all(shape(m) == shape(m0) for m in models) and all(x.shape == X_trains[0].shape for x in X_trains) and \
+    same = all(fam.shape(m) == fam.shape(m0) for m in models) and all(x.shape == X_trains[0].shape for x in X_trains) and \
         all((v is None) == (X_vals[0] is None) and (v is None or v.shape == X_vals[0].shape) for v in X_vals)
     n, T = int(X_trains[0].shape[0]), int(X_trains[0].shape[1])
     Bmax = min(int(batch_size), n)
     fused = same and R <= MAX_REPLICAS and n > 0 and all(
-        m.fused_eligible(criterion, optimizers[i], T=T, Bmax=Bmax, split_timeseries=split_timeseries)
-        for i, m in enumerate(models)) and len(set(id(m) for m in models)) == R
+        fam.eligible(m, criterion, optimizers[i], T, Bmax, split_timeseries) for i, m in enumerate(models)) and \
+        len(set(id(m) for m in models)) == R
     if not fused:
         if R > 1:  # nothing to share: fit one after the other (each may still take the fused route)
-            return [fit_navar_baselines([models[i]], [save_paths[i]], [X_trains[i]], criterion, [optimizers[i]],
-                                        [X_vals[i]], val_proportion, epochs, batch_size, check_every, lams[i], [rngs[i]],
-                                        verbose, split_timeseries)[0] for i in range(R)]
-        return [_fit_generic(m0, save_paths[0], X_trains[0], criterion, optimizers[0], X_vals[0], val_proportion, epochs,
-                             batch_size, split_timeseries, check_every, lams[0], rngs[0], verbose)]
+            return [_fit_navar_family(fam, [models[i]], [save_paths[i]], [X_trains[i]], criterion, [optimizers[i]],
+                                      [X_vals[i]], val_proportion, epochs, batch_size, check_every, lams[i], [rngs[i]],
+                                      verbose, split_timeseries)[0] for i in range(R)]
+        return [_fit_generic(fam, m0, save_paths[0], X_trains[0], criterion, optimizers[0], X_vals[0], val_proportion,
+                             epochs, batch_size, split_timeseries, check_every, lams[0], rngs[0], verbose)]
     # ---------------------------------------------------------------- fused
-    if R == 1:
-        pack, r0 = m0._slot()
-        rows = [r0]
-    else:
-        pack = NavarPack(models)
-        rows = list(range(R))
+    pack, rows, active = packs.acquire(models, optimizers, fam.pack)
     dev = pack.device
     for i in range(R):
-        pack.bind_optimizer(rows[i], optimizers[i])
         pack.lambda1[rows[i]] = float(lams[i])
-    active = None if (R > 1 or pack.R == 1) else rows
+    forecast = (lambda pred: pred[:, :, -1]) if fam.recurrent else (lambda pred: pred)
 
     def upload(xs):
-        xs = [torch.from_numpy(np.ascontiguousarray(x, dtype=np.float32)) for x in xs]
-        if R == 1:  # the pack may hold other rows: a zero stride serves this model's row
-            return xs[0].to(dev), 0
-        X = torch.stack(xs).to(dev)
-        return X, X[0].numel()
+        return packs.stack_upload([torch.from_numpy(np.ascontiguousarray(x, dtype=np.float32)) for x in xs], dev)
     Xtr, xps = upload(X_trains)
     do_val = val_proportion > 0.0 and X_vals[0] is not None
     if do_val:
@@ -481,7 +399,7 @@ def fit_navar_baselines(models, save_paths, X_trains, criterion, optimizers, X_v
         if t % check_every == 0:
             if do_val:
                 pred, _ = pack.forward(Xva, xps_va, 0, int(Xva.shape[-3]), active=active)
-                loss_val = [torch.nn.functional.mse_loss(pred[i], yva[i]) for i in range(R)]
+                loss_val = [torch.nn.functional.mse_loss(forecast(pred[i]), yva[i]) for i in range(R)]
             if verbose:
                 since = (torch.cat(mses[checked:], 1) + torch.cat(l1s[checked:], 1)).double().cpu().numpy()
                 for i in range(R):
@@ -497,3 +415,15 @@ def fit_navar_baselines(models, save_paths, X_trains, criterion, optimizers, X_v
         m.step_losses = (M[i], L[i])
         _save(m, save_paths[i])
     return loss_val
+
+
+_MLP = _Family("fit_navar_baselines", NavarPack, lambda m: (m.num_nodes, m.num_hidden, m.maxlags, m.hidden_layers),
+               lambda m, criterion, optimizer, T, Bmax, split: m.fused_eligible(criterion, optimizer, T=T, Bmax=Bmax,
+                                                                                split_timeseries=split), False)
+
+
+def fit_navar_baselines(models, save_paths, X_trains, criterion, optimizers, X_vals=None, val_proportion=0.0, epochs=200,
+                        batch_size=300, check_every=1000, lambda1=0, rngs=None, verbose=0, split_timeseries=False):
+    """NAVAR.fit (models/navar.py:57-125) for a list of models: _fit_navar_family."""
+    return _fit_navar_family(_MLP, models, save_paths, X_trains, criterion, optimizers, X_vals, val_proportion, epochs,
+                             batch_size, check_every, lambda1, rngs, verbose, split_timeseries)

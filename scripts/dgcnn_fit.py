@@ -24,7 +24,6 @@ import os
 import statistics
 import sys
 import tempfile
-import time
 
 import numpy as np
 import torch
@@ -34,29 +33,11 @@ for _p in (ROOT, os.path.join(ROOT, "redcliff-s-hypothesizing-dynamic-causal-gra
     if _p not in sys.path:
         sys.path.insert(0, _p)
 
+from fit_timing import event_ms, summary  # scripts/ leads the path of a script run
+
 SHAPES = {"d4ic": (10, 2, 1, 100, 5), "grid": (10, 2, 3, 250, 3)}  # nodes, F, layers, hid, classes
 B, N, T, NVAL = 128, 2048, 4, 256
 ADAM = dict(lr=1e-4, eps=1e-4, weight_decay=1e-4)
-
-
-def event_ms(fn):
-    """(ms between two HIP events around fn, host ms fn took to enqueue its work)"""
-    a, b = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-    torch.cuda.synchronize()
-    a.record()
-    t0 = time.perf_counter()
-    fn()
-    host = (time.perf_counter() - t0) * 1e3
-    b.record()
-    b.synchronize()
-    return a.elapsed_time(b), host
-
-
-def summary(s, epochs, steps):
-    med = statistics.median(s)
-    return {"median_ms": med, "min_ms": min(s), "max_ms": max(s), "spread_ms": max(s) - min(s), "samples_ms": s,
-            "us_per_step": {"median": 1e3 * med / (epochs * steps), "min": 1e3 * min(s) / (epochs * steps),
-                            "max": 1e3 * max(s) / (epochs * steps)}}
 
 
 def loaders(shape, seed):

@@ -23,7 +23,6 @@ import os
 import statistics
 import sys
 import tempfile
-import time
 
 import numpy as np
 import torch
@@ -33,31 +32,12 @@ for _p in (ROOT, os.path.join(ROOT, "redcliff-s-hypothesizing-dynamic-causal-gra
     if _p not in sys.path:
         sys.path.insert(0, _p)
 
+from fit_timing import event_ms, summary  # scripts/ leads the path of a script run
+
 FP32_PEAK_TFLOPS = 157.3
 P, H, C, TM, B, N = 10, 25, 2, 4, 128, 2048
 ADAM = dict(lr=5e-4, eps=1e-4, weight_decay=1e-4)
 COEFF = {"FORECAST_COEFF": 1.0, "ADJ_L1_REG_COEFF": 0.01, "DAGNESS_REG_COEFF": 0.0}
-
-
-def event_ms(fn):
-    """(ms between two HIP events around fn, host ms fn took to enqueue its work)"""
-    a, b = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-    torch.cuda.synchronize()
-    a.record()
-    t0 = time.perf_counter()
-    fn()
-    host = (time.perf_counter() - t0) * 1e3
-    b.record()
-    b.synchronize()
-    return a.elapsed_time(b), host
-
-
-def summary(s, epochs, steps):
-    med = statistics.median(s)
-    return {"median_ms": med, "min_ms": min(s), "max_ms": max(s), "spread_ms": max(s) - min(s), "samples_ms": s,
-            "us_per_epoch": {"median": 1e3 * med / epochs, "min": 1e3 * min(s) / epochs, "max": 1e3 * max(s) / epochs},
-            "us_per_step": {"median": 1e3 * med / (epochs * steps), "min": 1e3 * min(s) / (epochs * steps),
-                            "max": 1e3 * max(s) / (epochs * steps)}}
 
 
 def recordings(seed, n=N):
