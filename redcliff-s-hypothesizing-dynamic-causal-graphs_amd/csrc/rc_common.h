@@ -482,6 +482,19 @@ __device__ inline void rc_wait_leads(const StepCtx& c, float* ws, const unsigned
                 c.wait_dbg ? RC_WAIT_POLLS_DBG : RC_WAIT_POLLS);
 }
 
+// The value of a loaded register, opaque to the compiler at this point of the program: arithmetic
+// on it (a conversion, say) cannot be folded back into the block of its load, where it would wait
+// for the load.  No instruction is emitted; the memory clobber keeps it behind earlier stores.
+template <class T>
+__device__ inline T rc_keep(T v) {
+  asm volatile("" : "+v"(v) : : "memory");
+  return v;
+}
+
+// s_waitcnt vmcnt(0) as the builtin (gfx9 encoding: expcnt and lgkmcnt left at their maxima), which
+// the compiler's own wait insertion takes into account; an asm statement's wait it does not see.
+__device__ inline void rc_wait_loads() { __builtin_amdgcn_s_waitcnt(0x0F70); }
+
 __device__ inline float rc_wave_sum(float v) {
 #pragma unroll
   for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o, 64);
@@ -600,6 +613,36 @@ __device__ inline void rc_stage_all(S&&... s) {
   for (int r = 0; (s.active(r) || ...); ++r) {
     (s.load(r), ...);
     (s.store(r), ...);
+  }
+}
+
+// A segment of the first round only whose loads are whatever ld() issues (values that are no stream
+// of floats, into variables of the caller): they go out among the other segments' loads.
+template <class Ld>
+struct RcSegOnce {
+  Ld ld;
+  __device__ inline bool active(int r) const { return r == 0; }
+  __device__ inline void load(int r) {
+    if (r == 0) ld();
+  }
+  __device__ inline void store(int) {}
+};
+template <class Ld>
+__device__ inline RcSegOnce<Ld> rc_seg_once(Ld ld) {
+  return RcSegOnce<Ld>{ld};
+}
+
+// rc_stage_all with every round closed by a full wait.  A lane's stores have waited for its loads
+// already, but behind per-lane guards, so at the loop's back edge the compiler still counts the
+// round's loads as in flight and drains everything (loads issued ahead of the staging pass too)
+// before it reuses a register for the next round's first address -- on the first round as well.
+// With the round closed, loads issued ahead of the pass stay in flight beside its own.
+template <class... S>
+__device__ inline void rc_stage_all_closed(S&&... s) {
+  for (int r = 0; (s.active(r) || ...); ++r) {
+    (s.load(r), ...);
+    (s.store(r), ...);
+    rc_wait_loads();
   }
 }
 

@@ -45,6 +45,10 @@ __device__ inline int fq_tile(const RedcliffDims& d) { return d.p * d.L <= FQ_MA
 // slice t's fc1 with the lane chains of a 256-thread workgroup's four waves, the row-holding lanes
 // leave the slice sums in LDS and f1 = (part_0 + part_1) + fc1b after one barrier -- the order of
 // both other paths, without the store / drain / counter / reload exchange between workgroups.
+// Memory round trips on a workgroup's path: the staging pass (the BatchNorm statistics among its
+// loads), then the fc1 weights of the wave's first three column steps, requested when the staging
+// data has landed and in flight under BatchNorm, the Chebyshev rows and the graph convolution --
+// which read and write LDS only: the workspace copies of T and R are stored after the products.
 template <int NBT, int NT>
 __device__ __attribute__((always_inline)) void emb_fwd_body(const StepCtx& c, int bx, int SB, int w_lds, int cs, int zs, float* sm) {
   constexpr bool TEAM = NT == RC_EMB_TEAM_NT;
@@ -84,28 +88,36 @@ __device__ __attribute__((always_inline)) void emb_fwd_body(const StepCtx& c, in
     unsigned* cnt = reinterpret_cast<unsigned*>(ws + c.wo.ecnt);
     for (int e = tid; e < p * rc_nchunk(d); e += NT) cnt[e] = 0u;
   }
-  // BatchNorm statistics (torch forms the scale in double in train mode), issued first
+  // BatchNorm statistics (torch forms the scale in double in train mode): the loads only, as the
+  // first segment of the staging pass.  Their conversions and the scale follow the pass behind
+  // rc_keep(); a conversion folded into the load's block waits for the load there, a round trip of
+  // its own in front of the staging loads.
   RC_PHASE(c.ws, c.wo.total, bx, 1);
   const bool train = c.flags & RC_BN_TRAIN;
-  double st_mean = 0.0, st_var = 0.0;
+  double st_mean = 0.0, st_var = 0.0;  // train: the batch statistics
+  float rn_mean = 0.f, rn_var = 0.f;   // evaluation: the running ones
   float bw = 0.f, bb = 0.f;
-  if (tid < F) {
-    if (train) {
-      st_mean = c.bns[r * c.bnsr + tid];
-      st_var = c.bns[r * c.bnsr + F + tid];
-    } else {
-      st_mean = c.rm[r * F + tid];
-      st_var = c.rv[r * F + tid];
-    }
-    bw = E[c.eo.bnw + tid];
-    bb = E[c.eo.bnb + tid];
-  }
+  double bn_eps = 0.0;
   const float* S = ws + c.wo.S;
   const float* gw = E + c.eo.gcW;
   // Loads per thread per segment sized so that the common shapes stage in ONE round (a second
   // round is another memory latency on every workgroup's path): n p^2 <= 512 (C1(K=4) 300, TST 432),
   // n F H <= 5,120 (4,800), K M1 <= 1,024 (TST 576)
-  rc_stage_all(
+  rc_stage_all_closed(
+      rc_seg_once([&]() {
+        if (tid < F) {
+          if (train) {
+            st_mean = c.bns[r * c.bnsr + tid];
+            st_var = c.bns[r * c.bnsr + F + tid];
+          } else {
+            rn_mean = c.rm[r * F + tid];
+            rn_var = c.rv[r * F + tid];
+          }
+          bw = E[c.eo.bnw + tid];
+          bb = E[c.eo.bnb + tid];
+          bn_eps = c.hyp[r].bn_eps;  // (a load too: issued here, not in front of the scale)
+        }
+      }),
       rc_seg<2 / UD, NT>(n * p * p, [&](int e) { return S[e]; }, [&](int e, float v) { Sl[e] = v; }),
       rc_seg<20 / UD, NT>(w_lds ? nFH : 0, [&](int e) { return gw[e]; }, [&](int e, float v) { Wl[e] = v; }),
       // window rows are contiguous in the channel index: read (s, f, ch), store [s][ch][f]
@@ -120,11 +132,49 @@ __device__ __attribute__((always_inline)) void emb_fwd_body(const StepCtx& c, in
       rc_seg<1, NT>(M1 + K, [&](int e) { return e < M1 ? E[c.eo.fc1b + e] : E[c.eo.fc2b + e - M1]; },
                 [&](int e, float v) { fb1[e] = v; }));  // fb2 follows fb1
   RC_PHASE(c.ws, c.wo.total, bx, 2);
+  // fc1 weights: the first three column steps of this wave's first slice, those the slice has, are
+  // requested here -- after the staging loads have landed (a request among them is drained with them:
+  // the staging waits are full waits and loads return in order) and ahead of BatchNorm, the Chebyshev
+  // rows and the graph convolution, none of which touches global memory (w_lds), so the weights
+  // arrive while they run and nothing waits for them before the first fc1 product.
+  const float* W1 = E + c.eo.fc1W;
+  const int lane = tid & 63, wv = __builtin_amdgcn_readfirstlane(tid >> 6) & 3;  // (the wave of its team)
+  const int team = TEAM ? __builtin_amdgcn_readfirstlane(tid >> 8) : 0;
+  const int fz0 = TEAM ? min(team, Zs) : zlo, fz1 = TEAM ? min(team + 1, Zs) : zhi;  // this wave's fc1 slices
+  const int RW = (M1 + 3) / 4, m0 = wv * RW;
+  // Three buffers of column-step weights in rotation (p*H = 1,000 - 1,200 at C1 / TST is 16 - 19
+  // column steps in slices of four): a buffer is refilled right after it is multiplied, when the
+  // slice has the column step it would hold, and read three steps later.  No load is issued for a
+  // column step the slice does not have: a wait in front of a product would include it.  (Where a
+  // path with a refill meets one without, the compiler copies the buffer between registers and the
+  // copy waits for the refill; slices of up to three steps, D4IC's, refill nothing, and the fourth
+  // step of a 200-column slice is waited for one product later than it is requested: DESIGN 8.)
+  // Rows past M1 load row M1 - 1 (their sums are never stored) and a lane past the slice's end a
+  // clamped (valid) column that it multiplies by zero, so no load sits behind a condition of its own.
+  auto qend = [&](int z) { return min(p, (z + 1) * cs) * H; };  // fc1 columns of slice z: [z*cs*H, qend(z))
+  int qb = qend(fz0);
+  auto ldw = [&](float (&w)[16], int qn) {
+    const int qc = qn < qb ? qn : qb - 1;
+#pragma unroll
+    for (int j = 0; j < 16; ++j) w[j] = W1[(int64_t)min(m0 + j, M1 - 1) * pH + qc];
+  };
+  float wb0[16], wb1[16], wb2[16];
+  // Every earlier load has landed on every path here, and the compiler is told so: where paths with
+  // different loads in flight meet (a wave with no slice issues none), its wait in front of a later
+  // use of a statistics register would otherwise be counted for the path without the request and
+  // drain the request on the other.
+  rc_wait_loads();
+  auto ldw3 = [&](int qa) {  // the first three column steps of the slice [qa, qb)
+    ldw(wb0, qa + lane);
+    if (qa + 64 < qb) ldw(wb1, qa + lane + 64);
+    if (qa + 128 < qb) ldw(wb2, qa + lane + 128);
+  };
+  if (fz0 < fz1) ldw3(fz0 * cs * H);
   if (tid < F) {
     // torch CPU batch_norm: y = x * alpha + beta, alpha = invstd * gamma, beta = bias - mean * alpha
-    const float mean = (float)st_mean;
-    const float inv = train ? (float)(1.0 / sqrt(st_var + c.hyp[r].bn_eps))
-                            : 1.0f / sqrtf((float)st_var + (float)c.hyp[r].bn_eps);
+    const float mean = train ? (float)rc_keep(st_mean) : rc_keep(rn_mean);
+    const double eps = rc_keep(bn_eps);
+    const float inv = train ? (float)(1.0 / sqrt(rc_keep(st_var) + eps)) : 1.0f / sqrtf(rc_keep(rn_var) + (float)eps);
     const float a = inv * bw;
     alpha[tid] = a;
     beta[tid] = bb - mean * a;
@@ -136,7 +186,10 @@ __device__ __attribute__((always_inline)) void emb_fwd_body(const StepCtx& c, in
   }
   __syncthreads();
   RC_PHASE(c.ws, c.wo.total, bx, 3);
-  // Chebyshev filtering T_i = S_i x_bn (T_0 = x_bn exactly, as matmul(eye, x)), rows [ch0, ch1)
+  // Chebyshev filtering T_i = S_i x_bn (T_0 = x_bn exactly, as matmul(eye, x)), rows [ch0, ch1).
+  // T and R go to LDS only here and in the graph convolution: a global store inside these loops
+  // makes the compiler drain every load in flight (the fc1 weights) in front of the loop.  The
+  // workspace copies the backward reads are stored from LDS after the fc1 products (store_TR).
   const int cF = (ch1 - ch0) * F, cH = (ch1 - ch0) * H;
   // the slice width's multipliers (host-computed for the regular, the last and the whole width)
   const int cw = ch1 - ch0;
@@ -157,57 +210,49 @@ __device__ __attribute__((always_inline)) void emb_fwd_body(const StepCtx& c, in
       for (int cc = 0; cc < p; ++cc) v += Srow[cc] * xc[cc * F];
     }
     Tl[s * n * pF + rem] = v;
-    ws[c.wo.T + (int64_t)(b0 + s) * n * pF + rem] = v;
   }
   __syncthreads();
-  RC_PHASE(c.ws, c.wo.total, bx, 4);
-  // fc1 weights of the first column step are issued before the graph convolution runs
-  const float* W1 = E + c.eo.fc1W;
-  const int lane = tid & 63, wv = __builtin_amdgcn_readfirstlane(tid >> 6) & 3;  // (the wave of its team)
-  const int team = TEAM ? __builtin_amdgcn_readfirstlane(tid >> 8) : 0;
-  const int fz0 = TEAM ? min(team, Zs) : zlo, fz1 = TEAM ? min(team + 1, Zs) : zhi;  // this wave's fc1 slices
-  const int RW = (M1 + 3) / 4, m0 = wv * RW;
-  // three buffers of column-step weights in rotation (p*H = 1,000 - 1,200 at C1 / TST is 16 - 19
-  // column steps): each buffer is refilled right after it is multiplied and read two steps
-  // later, with no register moves in between (a move of a loading register waits for the load).
-  // Rows past M1 are wave-uniform zeros; a lane past p*H loads a clamped (valid) column that its
-  // masked multiply never uses, so no load sits behind a lane-varying condition.
-  auto qend = [&](int z) { return min(p, (z + 1) * cs) * H; };  // fc1 columns of slice z: [z*cs*H, qend(z))
-  int qb = qend(fz0);
-  auto ldw = [&](float (&w)[16], int qn) {
-    const int qc = qn < qb ? qn : qb - 1;
+  RC_PHASE(c.ws, c.wo.total, bx, 4);  // (trace builds: the next mark is 6, after the graph convolution)
+  // Z = sum_i T_i W_i ; R = relu(Z).  The loop is instantiated per address space of the weights
+  // (LDS or global): through a generic pointer every weight read is a flat load, which counts as a
+  // memory and an LDS access at once and ends each group of four in a full wait on both.
+  auto gconv = [&](auto* Wsrc) {
+    for (int e = tid; e < nb * cH; e += NT) {
+      const int s = dcH.div(e), rem = ch0 * H + (e - s * cH), ch = dH.div(rem), hh = rem - ch * H;
+      float a4[4] = {0.f, 0.f, 0.f, 0.f};  // four independent chains hide the LDS latency
+      for (int i = 0; i < n; ++i) {
+        const float* trow = Tl + (s * n + i) * pF + ch * F;
+        auto* wc = Wsrc + i * F * H + hh;
+        int f = 0;
+        for (; f + 3 < F; f += 4) {
 #pragma unroll
-    for (int j = 0; j < 16; ++j) w[j] = (j < RW && m0 + j < M1) ? W1[(int64_t)(m0 + j) * pH + qc] : 0.f;
-  };
-  float wb0[16], wb1[16], wb2[16];
-  if (fz0 < fz1) {
-    ldw(wb0, fz0 * cs * H + lane);
-    ldw(wb1, fz0 * cs * H + lane + 64);
-  }
-  RC_PHASE(c.ws, c.wo.total, bx, 5);
-  // Z = sum_i T_i W_i ; R = relu(Z)
-  const float* Wsrc = w_lds ? Wl : gw;
-  for (int e = tid; e < nb * cH; e += NT) {
-    const int s = dcH.div(e), rem = ch0 * H + (e - s * cH), ch = dH.div(rem), hh = rem - ch * H;
-    float a4[4] = {0.f, 0.f, 0.f, 0.f};  // four independent chains hide the LDS latency
-    for (int i = 0; i < n; ++i) {
-      const float* trow = Tl + (s * n + i) * pF + ch * F;
-      const float* wc = Wsrc + i * F * H + hh;
-      int f = 0;
-      for (; f + 3 < F; f += 4) {
-#pragma unroll
-        for (int u = 0; u < 4; ++u) a4[u] += trow[f + u] * wc[(f + u) * H];
+          for (int u = 0; u < 4; ++u) a4[u] += trow[f + u] * wc[(f + u) * H];
+        }
+        for (; f < F; ++f) a4[0] += trow[f] * wc[f * H];
       }
-      for (; f < F; ++f) a4[0] += trow[f] * wc[f * H];
+      Rl[s * pH + rem] = fmaxf((a4[0] + a4[1]) + (a4[2] + a4[3]), 0.f);
     }
-    const float v = fmaxf((a4[0] + a4[1]) + (a4[2] + a4[3]), 0.f);
-    Rl[s * pH + rem] = v;
-    ws[c.wo.R + (int64_t)(b0 + s) * pH + rem] = v;
-  }
+  };
+  if (w_lds)
+    gconv(Wl);
+  else
+    gconv(gw);
   __syncthreads();
+  // the workspace copies of T and R (read by the next launch: the kernel boundary orders them),
+  // from LDS, by every workgroup that formed rows of them
+  auto store_TR = [&]() {
+    for (int e = tid; e < nb * n * cF; e += NT) {
+      const int s = dncF.div(e), rs = e - s * n * cF, i = dcF.div(rs), rem = i * pF + ch0 * F + (rs - i * cF);
+      ws[c.wo.T + (int64_t)(b0 + s) * n * pF + rem] = Tl[s * n * pF + rem];
+    }
+    for (int e = tid; e < nb * cH; e += NT) {
+      const int s = dcH.div(e), rem = ch0 * H + (e - s * cH);
+      ws[c.wo.R + (int64_t)(b0 + s) * pH + rem] = Rl[s * pH + rem];
+    }
+  };
   RC_PHASE(c.ws, c.wo.total, bx, 6);
   // fc1: wave wv owns rows [wv*RW, wv*RW+RW) (RW <= 16); lanes split the slice's columns.
-  // The next column step's weights are loaded while the current one is multiplied.
+  // Later column steps' weights are loaded while the current one is multiplied.
   // one window per workgroup (the single fit) multiplies only its own column: NB = 1 accumulators
   const int jrow = (lane >> 2) & 15, mrow = m0 + jrow;
   const bool wrow = (lane & 3) == 0 && jrow < RW && mrow < M1;  // the lane that holds row mrow's sum
@@ -217,37 +262,48 @@ __device__ __attribute__((always_inline)) void emb_fwd_body(const StepCtx& c, in
     for (int z = fz0; z < fz1; ++z) {
       const int qa = z * cs * H;
       qb = qend(z);
-      if (z > fz0) {  // the first slice's first two column steps were issued before the graph convolution
-        ldw(wb0, qa + lane);
-        ldw(wb1, qa + lane + 64);
-      }
       float acc[16][NB];
 #pragma unroll
       for (int j = 0; j < 16; ++j)
 #pragma unroll
         for (int s = 0; s < NB; ++s) acc[j][s] = 0.f;
-      // column q of this lane (q ascending per lane: the same chains as one step per iteration)
+      // column q of this lane (q ascending per lane: the same chains as one step per iteration).
+      // A lane past the slice's end multiplies by zero instead of branching round the products: the
+      // sums start at +0 and never become -0, so with finite weights adding w * 0 leaves their bits
+      // (a non-finite weight in the slice's last column, which the lane that owns the column
+      // multiplies anyway, makes the row's sum NaN where the branch left Inf or NaN), and with no
+      // lane-dependent path round the uses of a buffer its refill waits for nothing.
       auto mul = [&](const float (&w)[16], int q) {
-        if (q < qb) {
-          float rv[NB];
+        const int qc = q < qb ? q : qb - 1;
+        float rv[NB];
 #pragma unroll
-          for (int s = 0; s < NB; ++s) rv[s] = s < nb ? Rl[s * pH + q] : 0.f;
-#pragma unroll
-          for (int j = 0; j < 16; ++j)
-#pragma unroll
-            for (int s = 0; s < NB; ++s) acc[j][s] += w[j] * rv[s];
+        for (int s = 0; s < NB; ++s) {
+          const float x = Rl[(s < nb ? s : 0) * pH + qc];
+          rv[s] = s < nb && q < qb ? x : 0.f;
         }
+#pragma unroll
+        for (int j = 0; j < 16; ++j)
+#pragma unroll
+          for (int s = 0; s < NB; ++s) acc[j][s] += w[j] * rv[s];
       };
       for (int q0 = qa; q0 < qb; q0 += 192) {  // wave-uniform steps of three column blocks
         const int q = q0 + lane;
-        ldw(wb2, q + 128);
         mul(wb0, q);
-        if (q0 + 64 >= qb) break;
-        ldw(wb0, q + 192);
-        mul(wb1, q + 64);
-        if (q0 + 128 >= qb) break;
-        ldw(wb1, q + 256);
-        mul(wb2, q + 128);
+        if (q0 + 192 < qb) ldw(wb0, q + 192);
+        if (q0 + 64 < qb) {
+          mul(wb1, q + 64);
+          if (q0 + 256 < qb) ldw(wb1, q + 256);
+        }
+        if (q0 + 128 < qb) {
+          mul(wb2, q + 128);
+          if (q0 + 320 < qb) ldw(wb2, q + 320);
+        }
+      }
+      // the next slice's first column steps (the first slice's were requested ahead of BatchNorm),
+      // into the same buffers, under this slice's reduce-scatter; a wave team has one slice
+      if (!TEAM && z + 1 < fz1) {
+        qb = qend(z + 1);
+        ldw3((z + 1) * cs * H);
       }
       // reduce-scatter of the 16 row partials over the 64 lanes: 17 shuffles per window instead of
       // 16 full reductions (96); afterwards lane l holds row (l >> 2) & 15 in every lane of its quad
@@ -304,7 +360,10 @@ __device__ __attribute__((always_inline)) void emb_fwd_body(const StepCtx& c, in
     unsigned* cnt = reinterpret_cast<unsigned*>(ws + c.wo.ecnt) + p * rc_nchunk(d) + 1 + b0;
     asm volatile("s_waitcnt vmcnt(0)" ::: "memory");  // every storing wave drains its partials
     __syncthreads();
-    if (tid == 0) last = __hip_atomic_fetch_add(cnt, 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) == (unsigned)(Zs - 1);
+    unsigned seen = 0u;
+    if (tid == 0) seen = __hip_atomic_fetch_add(cnt, 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+    store_TR();  // every slice's workgroup stores its rows, while the count's round trip is under way
+    if (tid == 0) last = seen == (unsigned)(Zs - 1);
     __syncthreads();
     if (!last) return;
     if (tid == 0) __hip_atomic_store(cnt, 0u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);  // re-armed for the next launch
@@ -329,6 +388,7 @@ __device__ __attribute__((always_inline)) void emb_fwd_body(const StepCtx& c, in
   }
   __syncthreads();
   RC_PHASE(c.ws, c.wo.total, bx, 7);
+  if (zs < 0) store_TR();  // beside fc2, which a few threads run (their stores' round trip runs under it)
   for (int e = tid; e < nb * K; e += NT) {
     const int s = e / K, k = e - s * K;
     const float* w2 = fc2s + k * M1;

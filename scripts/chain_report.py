@@ -7,7 +7,9 @@ the number of matrix-core instructions, how many of those directly follow a full
 (s_waitcnt lgkmcnt(0) as the previous instruction: an MFMA that waits for its own operands'
 round trip), and the number of double-precision vector instructions (v_*_f64*: the chip has no
 scalar double arithmetic, so uniform double math such as the Adam bias corrections' pow runs on
-the vector unit; static count, taken or not).  The assembly is read for these quantities only.
+the vector unit; static count, taken or not), and the number of flat loads and stores (flat_load* /
+flat_store*: accesses through a pointer whose address space the compiler does not know, which
+count as a memory and an LDS access at once).  The assembly is read for these quantities only.
 
   python scripts/chain_report.py [--filter SUBSTR] [--csrc DIR] [--keep DIR] [file.hip ...]
 """
@@ -71,7 +73,7 @@ def parse(path):
             vgprs[name] = int(m.group(1))
         m = _LABEL.match(raw)
         if m and not m.group(1).startswith(".L"):
-            cur = {"lane": 0, "mfma": 0, "mfma_wait": 0, "f64": 0}
+            cur = {"lane": 0, "mfma": 0, "mfma_wait": 0, "f64": 0, "flat": 0}
             kernels[m.group(1)] = cur
             prev = ""
             continue
@@ -94,6 +96,8 @@ def parse(path):
                 cur["mfma_wait"] += 1
         elif op.startswith("v_") and "_f64" in op:
             cur["f64"] += 1
+        elif op.startswith(("flat_load", "flat_store")):
+            cur["flat"] += 1
         prev = line
     out = {}
     for sym, k in kernels.items():
@@ -112,8 +116,8 @@ def main():
     ap.add_argument("--keep", default="", help="write the assembly files into this directory")
     a = ap.parse_args()
     files = a.files or sorted(os.path.join(a.csrc, f) for f in os.listdir(a.csrc) if f.endswith(".hip"))
-    print("%-58s %8s %5s %3s %7s %6s %6s %5s %9s %5s" %
-          ("kernel", "bytes", "vgpr", "occ", "scratch", "sspill", "lanemv", "mfma", "mfma@wait", "f64"))
+    print("%-58s %8s %5s %3s %7s %6s %6s %5s %9s %5s %5s" %
+          ("kernel", "bytes", "vgpr", "occ", "scratch", "sspill", "lanemv", "mfma", "mfma@wait", "f64", "flat"))
     with tempfile.TemporaryDirectory(prefix="rc_asm_") as tmp:
         if a.keep:
             os.makedirs(a.keep, exist_ok=True)
@@ -129,9 +133,9 @@ def main():
             if rows:
                 print("# %s" % os.path.basename(src))
             for nm, k in rows:
-                print("%-58s %8d %5d %3d %7d %6d %6d %5d %9d %5d" %
+                print("%-58s %8d %5d %3d %7d %6d %6d %5d %9d %5d %5d" %
                       (nm[:58], k["code"], k.get("vgpr", -1), k.get("occ", -1), k.get("scratch", -1), k["spill"],
-                       k["lane"], k["mfma"], k["mfma_wait"], k["f64"]))
+                       k["lane"], k["mfma"], k["mfma_wait"], k["f64"], k["flat"]))
 
 
 if __name__ == "__main__":
